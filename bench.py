@@ -1,8 +1,8 @@
 """Benchmark: StyleGAN2-ADA training throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 
 Workload (BASELINE.json configs[1] per GPU; configs[2] at N=8): the Claro job of the reference
 (src/bash/claro-*.sh:18 -> SG3/train_mi_multimodal.py): 256x256 1-channel images, conditional
@@ -22,7 +22,11 @@ K = 20 has 5 Greg and 2 Dreg (10 % Dreg steps against the schedule's 6.25 %, so 
 pessimistic).
 value = images processed by all ranks / max-over-ranks wall time of the K timed steps.
 
-Extra fields: `roofline` for the dominant kernel (the MFMA implicit-GEMM convolution of the 256^2
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR` also writes the
+state the last timed step left (dump_outputs) as DIR/<name>.npy.  Everything else is measured only with `--full`
+(after the timed region, so the headline figure is the same either way) and is null in a plain run's line.
+
+Extra fields (`--full`): `roofline` for the dominant kernel (the MFMA implicit-GEMM convolution of the 256^2
 layers -- the top-resolution synthesis layer at the run's own batch, so C4 / C5 report their 512^2 C=64 /
 1024^2 C=32 layers -- timed with HIP events on the launching stream after the timed region) and `cpu_baseline`
 (the CPU oracle restatement of the same iteration on the host cores, bounded sample, rank 0, N=1).
@@ -57,8 +61,13 @@ def parse():
     ap.add_argument('--c-dim', type=int, default=2)
     ap.add_argument('--map-depth', type=int, default=8)
     ap.add_argument('--fp16-dtype', default='fp16', choices=['fp16', 'bf16'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure the extra fields (roofline, roofline_families, '
+                         'cpu_baseline and, with several GPUs, dist.exchange); a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the state the last timed step left (dump_outputs) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip cpu_baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip roofline and roofline_families')
     ap.add_argument('--phase-timing', action='store_true')
     ap.add_argument('--graphs', default='auto', choices=['auto', 'on', 'off'],
                     help='HIP-graph replay of each phase, the bucket all_reduces captured into the phase graphs with '
@@ -158,6 +167,36 @@ def one_step(tr, args, device, real, real_c):
     lab = torch.randint(0, max(args.c_dim, 1), [n_ph, args.batch_gpu], device=device)
     c = torch.nn.functional.one_hot(lab, max(args.c_dim, 1)).float()[..., :args.c_dim]
     tr.step([real], [real_c], [[z[i]] for i in range(n_ph)], [[c[i]] for i in range(n_ph)])
+
+
+DUMP_BUDGET = 64 << 20    # bytes of .npy payload a --dump-outputs run may write in all
+DUMP_SAMPLE = 65536       # elements kept of a larger tensor
+
+
+def dump_outputs(tr, out_dir):
+    """What a caller of Trainer.step holds after the last timed step: every parameter and floating-point buffer of G,
+    D and G_ema, the ADA probability and the path-length mean, each as <out_dir>/<name>.npy in float32.  A tensor
+    of more than DUMP_SAMPLE elements (fewer where that many of every tensor would pass DUMP_BUDGET) is written as a
+    fixed sample of its flattened elements: sorted indices drawn without replacement from numpy's default_rng(0), so
+    the same elements in every run and every build.  The run's inputs are functions of the seeds (build: torch.manual_seed(0);
+    make_inputs), and the default deterministic reductions make the steps bitwise reproducible, so two runs with
+    the same arguments write the same files."""
+    os.makedirs(out_dir, exist_ok=True)
+    named = [(f'{n}.{k}', v) for n, m in (('G', tr.G), ('D', tr.D), ('G_ema', tr.G_ema))
+             for k, v in list(m.named_parameters()) + list(m.named_buffers()) if v.is_floating_point()]
+    if tr.augment_pipe is not None:
+        named.append(('augment_pipe.p', tr.augment_pipe.p))
+    named.append(('loss.pl_mean', tr.loss.pl_mean))
+    cap = min(DUMP_SAMPLE, DUMP_BUDGET // 4 // len(named))
+    picks = {}
+    for name, v in named:
+        a = v.detach().float()
+        if a.numel() > cap:
+            if a.numel() not in picks:
+                idx = np.sort(np.random.default_rng(0).choice(a.numel(), cap, replace=False))
+                picks[a.numel()] = torch.from_numpy(idx).to(a.device)
+            a = a.reshape(-1)[picks[a.numel()]]
+        np.save(os.path.join(out_dir, name + '.npy'), a.cpu().numpy())
 
 
 def _layer_launch(device, res, C, dtype, N=32):
@@ -514,8 +553,12 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)        # before anything below steps the trainer again
+
+    # everything past the headline figure takes runs of its own and is measured only with --full
     exch = None
-    if world > 1:
+    if args.full and world > 1:
         exch = exchange_diagnostics(tr, args, device, real, real_c, world)
     imgs = args.steps * args.batch_gpu * num_gpus
     value = imgs / elapsed
@@ -524,21 +567,21 @@ def main():
         phase_ms = {ph.name: round(ph.start_event.elapsed_time(ph.end_event), 2) for ph in tr.phases
                     if ph.start_event is not None}
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roof = roofline(device, args.res, args.cbase, torch.float16 if args.fp16_dtype == 'fp16' else torch.bfloat16,
                         args.batch_gpu)
     fams = None
-    if not args.no_roofline and args.res == 256:
+    if args.full and not args.no_roofline and args.res == 256:
         fams = roofline_families(device, torch.float16 if args.fp16_dtype == 'fp16' else torch.bfloat16)
     cpu = None
-    if rank == 0 and num_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and num_gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
     if rank == 0:
         line = {
             'metric': f'imgs/sec at {args.res}^2 bs{args.batch_gpu}/GPU StyleGAN2-ADA training (+ sec/kimg)',
             'value': round(value, 3), 'unit': 'imgs/s', 'n_gpus': num_gpus, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True,
-            'graphs': graphs, 'deterministic': args.deterministic == 'on',
+            'graphs': graphs, 'deterministic': args.deterministic == 'on', 'full': args.full,
             'scaling': 'weak', 'vs_baseline': None,
             'dtype': f'{args.fp16_dtype}+fp32 ({args.fp16_dtype} at the 4 highest resolutions, fp32 below; f32 accumulate)',
             'data': 'synthetic (U(-1,1) reals resident in HBM, device-drawn z, random one-hot c; random-init weights)',

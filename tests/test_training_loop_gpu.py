@@ -15,6 +15,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
+@pytest.fixture(autouse=True)
+def _fresh_stats_board(monkeypatch):
+    """The training loop is a process entry point: it calls training_stats.init_multiprocessing, which must come
+    before the process's first Collector.update().  Tests that ran earlier in the same session have used
+    collectors, so the loop gets the statistics board a fresh process starts with (the session's own comes back
+    afterwards)."""
+    from torch_utils import training_stats
+    monkeypatch.setattr(training_stats, '_board', training_stats._Board())
+
+
 class _ProjDetector(torch.nn.Module):
     """uint8 [N, 3, H, W] -> 16 features: 4x4 average pool, fixed random projection."""
 

@@ -27,7 +27,7 @@ if step smoke; then
 fi
 if step bench; then
     echo "== bench"
-    (cd "$R" && timeout -k 10 400 python -u bench.py > "$O/bench.log" 2>&1)
+    (cd "$R" && timeout -k 10 400 python -u bench.py --full > "$O/bench.log" 2>&1)
     rc=$?; tail -1 "$O/bench.log"; [ $rc -eq 0 ] || exit $rc
 fi
 if step parts; then
@@ -38,7 +38,7 @@ fi
 if step prof; then
     echo "== rocprofv3 kernel trace of the bench command"
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv \
-        -- python3 "$R/bench.py" --no-cpu-baseline > "$O/prof_bench.log" 2>&1
+        -- python3 "$R/bench.py" --full --no-cpu-baseline > "$O/prof_bench.log" 2>&1
     rc=$?; tail -1 "$O/prof_bench.log"; [ $rc -eq 0 ] || exit $rc
     f=$(find "$O/prof" -name 'run_kernel_stats.csv' | head -1)
     python3 "$R/profiles/prof_summary.py" "$(dirname "$f")" 45 > "$O/prof_summary.txt" 2>&1
@@ -50,13 +50,13 @@ if step prof; then
 fi
 if step c4; then
     echo "== C4 bench (512^2 3-ch, cbase 32768, bs16, fp16)"
-    (cd "$R" && timeout -k 10 500 python -u bench.py --res 512 --batch-gpu 16 --img-channels 3 --cbase 32768 --c-dim 0 \
+    (cd "$R" && timeout -k 10 500 python -u bench.py --full --res 512 --batch-gpu 16 --img-channels 3 --cbase 32768 --c-dim 0 \
         > "$O/c4_bench.log" 2>&1)
     rc=$?; tail -1 "$O/c4_bench.log"; [ $rc -eq 0 ] || exit $rc
 fi
 if step c5; then
     echo "== C5 bench (1024^2 3-ch, cbase 32768, bs8, bf16)"
-    (cd "$R" && timeout -k 10 500 python -u bench.py --res 1024 --batch-gpu 8 --img-channels 3 --cbase 32768 --c-dim 0 \
+    (cd "$R" && timeout -k 10 500 python -u bench.py --full --res 1024 --batch-gpu 8 --img-channels 3 --cbase 32768 --c-dim 0 \
         --fp16-dtype bf16 > "$O/c5_bench.log" 2>&1)
     rc=$?; tail -1 "$O/c5_bench.log"; [ $rc -eq 0 ] || exit $rc
 fi
