@@ -74,6 +74,101 @@ __device__ __forceinline__ f32x4 mma(v8<T> a, v8<T> b, f32x4 c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
+// The direct epilogue of the stride-1 halo kernels (DIR below, and the LDS-DMA form): the accumulators are in the
+// swapped-operand layout with the weight rows in p_chan order, so lane (l16, q) holds, per pixel fragment i and
+// channel half h, channels o0 + 32 h + 8 q + e (e = 4 jj + r) of tile pixel wave PXW + 16 i + l16: the fused math in
+// registers and 16-byte stores straight from them.  `red`: LDS that no wave still reads, [BN] floats (atomic dot) or
+// [4 waves][BN] (deterministic dot: the tile's slot of det_dot).
+template <typename T, int TW, int NFR, bool EPI>
+__device__ __forceinline__ void halo_direct_epilogue(const Conv3Args& a, const f32x4 (&acc)[NFR][4], float* red, int n,
+                                                     int tile, int ty0, int tx0, int o0) {
+    constexpr int PXW = NFR * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lq = lane >> 4, l16 = lane & 15;
+    float dsc[2][8], bsc[2][8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int o = o0 + 32 * h + 8 * lq + e;
+            dsc[h][e] = (EPI && a.out_scale) ? a.out_scale[(int64_t)n * a.Cout + o] : 1.f;
+            bsc[h][e] = (EPI && a.bias) ? (float)(T)a.bias[o] : 0.f;
+        }
+    typedef T vec8d __attribute__((ext_vector_type(8)));
+    const bool want_dot = a.dot_out != nullptr, atom = want_dot && !a.det_dot;
+    if (atom) {
+        if (tid < BN) red[tid] = 0.f;
+        __syncthreads();
+    }
+    float dacc[2][8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dacc[h][e] = 0.f;
+    T* y = (T*)a.y;
+    T* yr = (T*)a.y_raw;
+    const T* dsrc = (const T*)a.dot_src;
+    const T* nz = (const T*)a.noise;
+#pragma unroll
+    for (int i = 0; i < NFR; ++i) {
+        const int m = wave * PXW + i * 16 + l16;
+        const int py = m / TW, px = m - py * TW;
+        const int oy = ty0 + py, ox = tx0 + px;
+        const bool ok = oy < a.OH && ox < a.OW;
+        const int64_t pix = ((int64_t)n * a.OH + (ok ? oy : 0)) * a.OW + (ok ? ox : 0);
+        const float nv = (EPI && nz) ? (float)nz[pix] * a.noise_gain : 0.f;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            vec8d yv, rv;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float v = acc[i][2 * h + (e >> 2)][e & 3];
+                rv[e] = (T)v;
+                if (EPI) {
+                    v = v * dsc[h][e] + nv + bsc[h][e];
+                    if (a.act == 1) v = v > 0.f ? v : v * a.alpha;
+                    v *= a.gain;
+                    if (a.clamp >= 0.f) v = fminf(fmaxf(v, -a.clamp), a.clamp);
+                }
+                yv[e] = (T)v;
+            }
+            if (!ok) continue;
+            const int64_t dst = pix * a.Cout + o0 + 32 * h + 8 * lq;
+            *(vec8d*)(y + dst) = yv;
+            if (yr) *(vec8d*)(yr + dst) = rv;
+            if (want_dot) {
+                const vec8d sv = *(const vec8d*)(dsrc + dst);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dacc[h][e] += (float)rv[e] * (float)sv[e];
+            }
+        }
+    }
+    if (want_dot) {
+        // the 16 pixel lanes of a channel group by shuffles; then the 4 waves: LDS atomics + one global atomic
+        // per channel, or (deterministic mode) wave partials added in wave order into the tile's slot
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float v = dacc[h][e];
+                v += __shfl_xor(v, 1);
+                v += __shfl_xor(v, 2);
+                v += __shfl_xor(v, 4);
+                v += __shfl_xor(v, 8);
+                if (l16 == 0) {
+                    if (atom) atomicAdd(&red[32 * h + 8 * lq + e], v);
+                    else red[wave * BN + 32 * h + 8 * lq + e] = v;
+                }
+            }
+        __syncthreads();
+        if (tid < BN) {
+            if (atom) atomicAdd(&a.dot_out[(int64_t)n * a.Cout + o0 + tid], red[tid]);
+            else a.det_dot[(int64_t)tile * a.Cout + o0 + tid] = ((red[tid] + red[BN + tid]) + red[2 * BN + tid]) +
+                                                                 red[3 * BN + tid];
+        }
+    }
+}
+
 // TW: tile width (pixels); TH = 256 / TW.  4 waves, each owns 64 consecutive tile pixels x 64 channels.
 // NBUF = 2: double-buffered chunks (1 workgroup / CU); NBUF = 1: single buffer, 2 workgroups / CU
 // overlap each other's staging (better when Cin spans only a couple of chunks).
@@ -231,91 +326,8 @@ __global__ __launch_bounds__(256, 3 - NBUF) void conv3x3_halo_kernel(Conv3Args a
     }
 
     if constexpr (DIR) {
-        // lane (l16, q): pixel wave PXW + 16 i + l16 of the tile, channels o0 + 32 h + 8 q + e (e = 4 jj + r)
-        float dsc[2][8], bsc[2][8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int o = o0 + 32 * h + 8 * lq + e;
-                dsc[h][e] = (EPI && a.out_scale) ? a.out_scale[(int64_t)n * a.Cout + o] : 1.f;
-                bsc[h][e] = (EPI && a.bias) ? (float)(T)a.bias[o] : 0.f;
-            }
-        typedef T vec8d __attribute__((ext_vector_type(8)));
-        const bool want_dot = a.dot_out != nullptr, atom = want_dot && !a.det_dot;
-        float* red = (float*)smem;                 // dot partial sums (the halo buffer is free after the loop):
-                                                   // [BN] (atomic mode), [4 waves][BN] (deterministic mode)
-        if (atom) {
-            if (tid < BN) red[tid] = 0.f;
-            __syncthreads();
-        }
-        float dacc[2][8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) dacc[h][e] = 0.f;
-        T* y = (T*)a.y;
-        T* yr = (T*)a.y_raw;
-        const T* dsrc = (const T*)a.dot_src;
-        const T* nz = (const T*)a.noise;
-#pragma unroll
-        for (int i = 0; i < NFR; ++i) {
-            const int m = wave * PXW + i * 16 + l16;
-            const int py = m / TW, px = m - py * TW;
-            const int oy = ty0 + py, ox = tx0 + px;
-            const bool ok = oy < a.OH && ox < a.OW;
-            const int64_t pix = ((int64_t)n * a.OH + (ok ? oy : 0)) * a.OW + (ok ? ox : 0);
-            const float nv = (EPI && nz) ? (float)nz[pix] * a.noise_gain : 0.f;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                vec8d yv, rv;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float v = acc[i][2 * h + (e >> 2)][e & 3];
-                    rv[e] = (T)v;
-                    if (EPI) {
-                        v = v * dsc[h][e] + nv + bsc[h][e];
-                        if (a.act == 1) v = v > 0.f ? v : v * a.alpha;
-                        v *= a.gain;
-                        if (a.clamp >= 0.f) v = fminf(fmaxf(v, -a.clamp), a.clamp);
-                    }
-                    yv[e] = (T)v;
-                }
-                if (!ok) continue;
-                const int64_t dst = pix * a.Cout + o0 + 32 * h + 8 * lq;
-                *(vec8d*)(y + dst) = yv;
-                if (yr) *(vec8d*)(yr + dst) = rv;
-                if (want_dot) {
-                    const vec8d sv = *(const vec8d*)(dsrc + dst);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) dacc[h][e] += (float)rv[e] * (float)sv[e];
-                }
-            }
-        }
-        if (want_dot) {
-            // the 16 pixel lanes of a channel group by shuffles; then the 4 waves: LDS atomics + one global atomic
-            // per channel, or (deterministic mode) wave partials added in wave order into the tile's slot
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float v = dacc[h][e];
-                    v += __shfl_xor(v, 1);
-                    v += __shfl_xor(v, 2);
-                    v += __shfl_xor(v, 4);
-                    v += __shfl_xor(v, 8);
-                    if (l16 == 0) {
-                        if (atom) atomicAdd(&red[32 * h + 8 * lq + e], v);
-                        else red[wave * BN + 32 * h + 8 * lq + e] = v;
-                    }
-                }
-            __syncthreads();
-            if (tid < BN) {
-                if (atom) atomicAdd(&a.dot_out[(int64_t)n * a.Cout + o0 + tid], red[tid]);
-                else a.det_dot[(int64_t)tile * a.Cout + o0 + tid] = ((red[tid] + red[BN + tid]) + red[2 * BN + tid]) +
-                                                                     red[3 * BN + tid];
-            }
-        }
+        // (the halo buffer is free after the loop: the dot's partial sums)
+        halo_direct_epilogue<T, TW, NFR, EPI>(a, acc, (float*)smem, n, tile, ty0, tx0, o0);
         return;
     }
     // ---- epilogue: fused math in registers, transpose through LDS, 16-byte row stores ----
@@ -430,19 +442,12 @@ __global__ __launch_bounds__(256, 3 - NBUF) void conv3x3_halo_kernel(Conv3Args a
     }
 }
 
-template <typename T, int TW, bool SI, bool EPI, int NBUF, int S = 1, bool DIR = false>
-int launch3_k(const Conv3Args& a, hipStream_t s) {
-    constexpr int TH = S == 1 ? 256 / TW : 4;
-    size_t lds = NBUF * (size_t)((S * (TW - 1) + 3) * (S * (TH - 1) + 3) * PX + 9 * BN * PX) * sizeof(T);
-    if (!DIR) lds = std::max(lds, (size_t)2 * TW * TH * (BN + 8) * sizeof(T) + BN * sizeof(float));   // epilogue tiles
-    auto kern = conv3x3_halo_kernel<T, TW, SI, EPI, NBUF, S, DIR>;
-    static bool attr_set = false;   // benign race: idempotent attribute
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
+// One workgroup per 256-pixel tile and 64 output channels; in deterministic mode the dot's tile partials go to slots
+// [tile][Cout] and are summed per sample in tile order.
+template <typename K>
+int launch_halo_tiles(K kern, size_t lds, const Conv3Args& a, hipStream_t s) {
     dim3 grid(a.N * a.tiles_x * a.tiles_y, (a.Cout + BN - 1) / BN);
-    if (a.dot_out && det_on()) {     // the dot's tile partials by slot, summed per sample in tile order
+    if (a.dot_out && det_on()) {
         Conv3Args b = a;
         DetArena arena;
         const int tps = a.tiles_x * a.tiles_y;
@@ -456,6 +461,20 @@ int launch3_k(const Conv3Args& a, hipStream_t s) {
     }
     kern<<<grid, 256, lds, s>>>(a);
     return launch_status("sg2_conv3x3");
+}
+
+template <typename T, int TW, bool SI, bool EPI, int NBUF, int S = 1, bool DIR = false>
+int launch3_k(const Conv3Args& a, hipStream_t s) {
+    constexpr int TH = S == 1 ? 256 / TW : 4;
+    size_t lds = NBUF * (size_t)((S * (TW - 1) + 3) * (S * (TH - 1) + 3) * PX + 9 * BN * PX) * sizeof(T);
+    if (!DIR) lds = std::max(lds, (size_t)2 * TW * TH * (BN + 8) * sizeof(T) + BN * sizeof(float));   // epilogue tiles
+    auto kern = conv3x3_halo_kernel<T, TW, SI, EPI, NBUF, S, DIR>;
+    static bool attr_set = false;   // benign race: idempotent attribute
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
+    }
+    return launch_halo_tiles(kern, lds, a, s);
 }
 
 template <typename T, int TW, bool SI, bool EPI, int NBUF, int S = 1>
@@ -1840,6 +1859,188 @@ int launch_c32r_raw(const Conv3Args& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// LDS-DMA form of conv3x3_halo_kernel<T, 32, ., ., 1, 1, DIR> (stride 1, W >= 32, Cin % 32 == 0, Cout % 64 == 0): the
+// same 32 x 8 pixel x 64 channel workgroup tile, wave tile, MFMA order (chunks ascending, taps in (ky, kx) order) and
+// direct epilogue, so y, y_raw and the deterministic dot are bitwise those of the register-staged kernel.  What
+// differs is how the operands reach LDS and how the fragments are addressed:
+//   * no operand passes through VGPRs: halo and weights arrive by buffer_load ... lds (16 B a lane, 1 KiB a
+//     wave-instruction).  The LDS image is lane-linear, so the swz64 XOR sits in the SOURCE address (slot row p, piece
+//     slot q' receives source piece q' ^ ((p >> 1) & 2)); pixels outside the image and the pad positions of a halo
+//     row have base INT_MIN (out of range with any chunk offset added: zeros, sg2_common.h make_rsrc).  The per-lane
+//     source offsets are fixed per workgroup; a stage adds a scalar chunk / tap-row offset;
+//   * a stage is one tap row (ky) of a chunk: 3 x 64 weight rows (12 KiB, 3 DMAs a wave) in a 2-slot ring, plus a
+//     third of the NEXT chunk's halo (2 DMAs a wave; the modulated form: a half in each of the first two stages) into
+//     the other of two halo slots -- the DMAs are issued one stage ahead of the MFMAs that read them, across one raw
+//     s_barrier per stage (vmcnt(0) there retires exactly the stage about to be read);
+//   * the halo row pitch is 36 positions: 36 r = 4 (r & 1) mod 8, so the swizzle bit of a fragment read is a
+//     per-lane constant of kx XOR the compile-time row parity -- six per-lane bases, every read base + immediate;
+//   * the modulation (SCALE_IN): in_scale rounded to T sits in LDS (loaded under the first DMAs); a stage after its
+//     DMAs landed, each lane scales the 16 bytes it fetched in place (x * round(s), rounded once: scale_h below) --
+//     six 16-byte pieces a lane and chunk, no extra barrier.  (Multiplying every pixel fragment after its ds_read
+//     instead -- 144 v_pk_mul_f16 per wave and chunk -- only tied the register-staged kernel.)
+// LDS: 2 x 24 KiB halo + 2 x 12 KiB weights + 2 KiB scales + 1 KiB dot partials = 75 KiB, two workgroups per CU.
+constexpr int D_TW = 32, D_TH = 8, D_PITCH = 36;
+constexpr int D_HPOS = (D_TH + 2) * D_PITCH;                // 360 halo positions (34 used per row)
+constexpr int D_HDMA = 6;                                   // halo DMAs per wave and chunk (24 KiB, 22.5 used)
+constexpr int D_HSLOT = D_HDMA * 4 * 1024;
+constexpr int D_WDMA = 3;                                   // weight DMAs per wave and stage
+constexpr int D_WSLOT = 3 * BN * 64;
+constexpr int D_SCIN = 1024;                                // modulated form: Cin <= D_SCIN (the scale table)
+constexpr size_t D_LDS = 2 * D_HSLOT + 2 * D_WSLOT + D_SCIN * 2 + 4 * BN * sizeof(float);
+static_assert(D_HPOS * 64 <= D_HSLOT && D_WSLOT == D_WDMA * 4 * 1024 && 2 * D_LDS <= 160 * 1024, "halo DMA LDS");
+
+template <typename T, bool SCALE_IN, bool EPI>
+__global__ __launch_bounds__(256, 2) void conv3x3_halo_dma_kernel(Conv3Args a) {
+    constexpr int NFR = 4;
+    constexpr int HPARTS = SCALE_IN ? 2 : 3, HPD = D_HDMA / HPARTS;   // a chunk's halo: issued over HPARTS stages
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    char* hs = smem_raw;                                    // [2][D_HSLOT]
+    char* ws = smem_raw + 2 * D_HSLOT;                      // [2][D_WSLOT]
+    T* stab = (T*)(ws + 2 * D_WSLOT);                       // [Cin] in_scale of sample n, rounded to T
+    float* red = (float*)(ws + 2 * D_WSLOT + D_SCIN * 2);   // the epilogue's dot partials
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lq = lane >> 4, l16 = lane & 15;
+    const int tile = blockIdx.x;
+    const int n = tile / (a.tiles_x * a.tiles_y);
+    const int tr = tile - n * a.tiles_x * a.tiles_y;
+    const int ty0 = (tr / a.tiles_x) * D_TH, tx0 = (tr % a.tiles_x) * D_TW;
+    const int o0 = blockIdx.y * BN;
+    const int nchunks = a.Cin / CK;
+
+    // DMA lanes: instruction u of wave w fills slot rows (4 u + w) * 16 + lane / 4, piece slot lane % 4
+    const __amdgpu_buffer_rsrc_t rxb = make_rsrc(a.x, (int64_t)a.N * a.H * a.W * a.Cin * (int64_t)sizeof(T));
+    const __amdgpu_buffer_rsrc_t rwb = make_rsrc(a.w, (int64_t)a.Cout * 9 * a.Cin * (int64_t)sizeof(T));
+    int hbase[D_HDMA], wbase[D_WDMA];
+#pragma unroll
+    for (int u = 0; u < D_HDMA; ++u) {
+        const int p = (u * 4 + wave) * 16 + (lane >> 2);
+        const int j = (lane & 3) ^ ((p >> 1) & 2);
+        const int hy = p / D_PITCH, hx = p - hy * D_PITCH;
+        const int iy = ty0 - 1 + hy, ix = tx0 - 1 + hx;
+        const bool ok = p < D_HPOS && hx < D_TW + 2 && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+        hbase[u] = ok ? (((n * a.H + iy) * a.W + ix) * a.Cin + j * 8) * (int)sizeof(T) : (int)0x80000000;
+    }
+#pragma unroll
+    for (int u = 0; u < D_WDMA; ++u) {                      // rows 64 u .. + 63: tap kx = u of the stage's tap row
+        const int r = (u * 4 + wave) * 16 + (lane >> 2);
+        const int j = (lane & 3) ^ ((r >> 1) & 2);
+        wbase[u] = (((o0 + p_chan(r & (BN - 1))) * 9 + u) * a.Cin + j * 8) * (int)sizeof(T);
+    }
+    auto issue_w = [&](int chunk, int ky, int slot) {
+        const int off = (ky * 3 * a.Cin + chunk * CK) * (int)sizeof(T);
+#pragma unroll
+        for (int u = 0; u < D_WDMA; ++u)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rwb, (lds_ptr_t)(ws + slot * D_WSLOT + (u * 4 + wave) * 1024), 16,
+                                                     wbase[u] + off, 0, 0, 0);
+    };
+    auto issue_h = [&](int chunk, int part, int slot) {
+        const int off = chunk * CK * (int)sizeof(T);
+#pragma unroll
+        for (int v = 0; v < HPD; ++v) {
+            const int u = part * HPD + v;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rxb, (lds_ptr_t)(hs + slot * D_HSLOT + (u * 4 + wave) * 1024), 16,
+                                                     hbase[u] + off, 0, 0, 0);
+        }
+    };
+    // The modulation: x * s.to(x.dtype) (networks_stylegan2.py:69; s rounded first, one rounding after -- the product
+    // the register path forms at its LDS write), in place on the 16 bytes this lane's own DMAs brought, once they
+    // landed (this wave's vmcnt(0)); the stage barrier before the chunk's first read publishes it.  A lane's source
+    // piece is j = (lane & 3) ^ 2 ((lane >> 4) & 1) in every instruction (bit 2 of the slot row is bit 2 of lane / 4).
+    auto scale_h = [&](int chunk, int part, int slot) {
+        typedef T vec8 __attribute__((ext_vector_type(8)));
+        const int j = (lane & 3) ^ (((lane >> 4) & 1) << 1);
+        const vec8 sv = *(const vec8*)(stab + chunk * CK + j * 8);
+#pragma unroll
+        for (int v = 0; v < HPD; ++v) {
+            vec8* p = (vec8*)(hs + slot * D_HSLOT + ((part * HPD + v) * 4 + wave) * 1024 + lane * 16);
+            vec8 x8 = *p;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x8[e] = (T)((float)x8[e] * (float)sv[e]);
+            *p = x8;
+        }
+    };
+
+    // fragment bases: pixel fragment i of the wave is tile row 2 wave + (i >> 1), columns 16 (i & 1) + l16; at tap
+    // (ky, kx) it reads position P = (2 wave + (i >> 1) + ky) * 36 + 16 (i & 1) + l16 + kx, whose swizzle bit is
+    // bit 2 of P = ((i >> 1) + ky) & 1 XOR bit 2 of (l16 + kx)
+    int aoff[3][2];
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+        for (int par = 0; par < 2; ++par) {
+            const int v = l16 + kx;
+            aoff[kx][par] = (wave * 2 * D_PITCH + v) * 64 + ((lq ^ ((((v >> 2) & 1) ^ par) << 1)) << 4);
+        }
+    const int b_lane = swz64(l16, lq);                      // + (kx * BN + j * 16) * 64: the same swizzle
+
+    f32x4 acc[NFR][4];
+#pragma unroll
+    for (int i = 0; i < NFR; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+    for (int part = 0; part < HPARTS; ++part) issue_h(0, part, 0);
+    issue_w(0, 0, 0);
+    if (SCALE_IN) {
+        // the scale table, under the first DMAs' latency (plain loads and __syncthreads both drain vmcnt here, which
+        // the first scale pass needs anyway; nowhere else in the kernel)
+        for (int c = tid; c < a.Cin; c += 256) stab[c] = (T)a.in_scale[(int64_t)n * a.Cin + c];
+        __syncthreads();
+        wait_vm<0>();
+#pragma unroll
+        for (int part = 0; part < HPARTS; ++part) scale_h(0, part, 0);
+    }
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const bool more = ch + 1 < nchunks;
+        const char* hb = hs + (ch & 1) * D_HSLOT;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int wslot = (ch + ky) & 1;                // stage 3 ch + ky
+            wait_vm<0>();                                   // this wave's DMAs of the stage (issued one stage ago)
+            __builtin_amdgcn_s_waitcnt(0xc07f);             // lgkmcnt(0): the last stage's fragment reads, the table
+            __builtin_amdgcn_s_barrier();                   // every wave's landed; the other slots are free
+            if (ky < 2) issue_w(ch, ky + 1, wslot ^ 1);
+            else if (more) issue_w(ch + 1, 0, wslot ^ 1);
+            if (more && ky < HPARTS) issue_h(ch + 1, ky, (ch + 1) & 1);
+            const char* wb = ws + wslot * D_WSLOT + b_lane;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                v8<T> af[NFR], bfr[4];
+#pragma unroll
+                for (int i = 0; i < NFR; ++i) {
+                    const int row = (i >> 1) + ky;
+                    af[i] = *(const v8<T>*)(hb + aoff[kx][row & 1] + (row * D_PITCH + (i & 1) * 16) * 64);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bfr[j] = *(const v8<T>*)(wb + (kx * BN + j * 16) * 64);
+#pragma unroll
+                for (int i = 0; i < NFR; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = mma<T>(bfr[j], af[i], acc[i][j]);
+            }
+            // the part of the next chunk's halo that the last stage issued: landed at this stage's wait
+            if (SCALE_IN && more && ky >= 1) scale_h(ch + 1, ky - 1, (ch + 1) & 1);
+        }
+    }
+    // (no DMA is outstanding: the last stage issued none)
+    halo_direct_epilogue<T, D_TW, NFR, EPI>(a, acc, red, n, tile, ty0, tx0, o0);
+}
+
+template <typename T, bool SI, bool EPI>
+int launch_halo_dma(const Conv3Args& a, hipStream_t s) {
+    auto kern = conv3x3_halo_dma_kernel<T, SI, EPI>;
+    static bool attr_set = false;   // benign race: idempotent attribute
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)D_LDS);
+        attr_set = true;
+    }
+    return launch_halo_tiles(kern, D_LDS, a, s);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Stride-2 / pad-0 3x3 conv of the wide discriminator down layers (conv2d_resample's down-2 plan after its FIR,
 // :94-109: the D blocks' conv1 at 128^2 .. 32^2 outputs, Cin 64 .. 256 -> Cout = 2 Cin), round 5.  The 32 x 4 halo
 // form above restages a tile's 9 x 64 x 32 weights per 128 output pixels and ran these shapes at 0.10-0.18 of the
@@ -2093,6 +2294,22 @@ int dispatch(Conv3Args& a, hipStream_t s, int stride) {
     // load latency; measured 1.3-1.4x faster than a double-buffered single workgroup per CU at C >= 128
     // (gpurun_out/nbuf.log; SG2_HALO_NBUF=2 selects the double-buffered form)
     const int nbuf = force_nbuf ? force_nbuf : 1;
+    {
+        // the LDS-DMA form of the 32 x 8 tile with the direct epilogue (SG2_HALO_DMA=0: off; it stands in for the
+        // direct-epilogue kernel only, so SG2_HALO_DIRECT=0 and SG2_HALO_NBUF keep their meaning); read per launch:
+        // tests and A/Bs switch it in one process
+        const char* ed = getenv("SG2_HALO_DMA");
+        const char* e1 = getenv("SG2_HALO_DIRECT");
+        if ((!ed || atoi(ed) != 0) && (!e1 || atoi(e1) != 0) && !force_nbuf && TW == 32 && a.Cin % CK == 0 &&
+            a.Cout % BN == 0 && a.Cin <= 16384 && (!si || a.Cin <= D_SCIN) &&
+            ((uintptr_t)a.y % 16) == 0 && ((uintptr_t)a.y_raw % 16) == 0 && ((uintptr_t)a.dot_src % 16) == 0 &&
+            (int64_t)a.N * a.H * a.W * a.Cin * (int64_t)sizeof(T) < 0x7fff0000ll &&
+            (int64_t)a.N * a.H * a.W * a.Cout * (int64_t)sizeof(T) < 0x7fff0000ll) {
+            if (si) { if (epi) return launch_halo_dma<T, true, true>(a, s); return launch_halo_dma<T, true, false>(a, s); }
+            if (epi) return launch_halo_dma<T, false, true>(a, s);
+            return launch_halo_dma<T, false, false>(a, s);
+        }
+    }
 #define L3(TWV, SIV, EPIV) return nbuf == 1 ? launch3<T, TWV, SIV, EPIV, 1>(a, s) : launch3<T, TWV, SIV, EPIV, 2>(a, s)
     if (TW == 32) {
         if (si) { if (epi) L3(32, true, true); else L3(32, true, false); }
