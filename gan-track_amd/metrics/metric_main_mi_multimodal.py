@@ -1,7 +1,9 @@
 """Metric registry of the training loop.  Drop-in for SG3/metrics/metric_main_mi_multimodal.py:27-95: the module
 keeps the reference's entry points (register_metric, is_valid_metric, list_valid_metrics, calc_metric,
 report_metric) and its output contract (one JSON line per evaluation appended to
-<run_dir>/metric-<modality>-<metric>.jsonl); the FID metrics are the two the Claro / Pelvis runs name."""
+<run_dir>/metric-<modality>-<metric>.jsonl); the FID metrics are the two the Claro / Pelvis runs name, the
+precision / recall metrics (pr50k3_full, pr50k3) the one further metric the reference adapted to its per-modality
+evaluation."""
 import json
 import os
 import time
@@ -11,6 +13,7 @@ import torch
 import dnnlib
 from . import metric_utils
 from . import frechet_inception_distance
+from . import precision_recall
 
 
 class _Registry:
@@ -96,3 +99,21 @@ def fid50k_full(opts):
 @register_metric
 def fid50k(opts):
     return _fid(opts, 'fid50k', 50000, None)
+
+
+@register_metric
+def pr50k3_full(opts):
+    """Precision / recall, k = 3, against up to 200k real images (SG3/metrics/metric_main_mi_multimodal.py:103-106)."""
+    opts.dataset_kwargs.update(max_size=None, xflip=False)
+    precision, recall = precision_recall.compute_pr(opts, max_real=200000, num_gen=50000, nhood_size=3,
+                                                    row_batch_size=10000, col_batch_size=10000)
+    return dict(pr50k3_full_precision=precision, pr50k3_full_recall=recall)
+
+
+@register_metric
+def pr50k3(opts):
+    """Precision / recall, k = 3, against 50k real images (:147-150)."""
+    opts.dataset_kwargs.update(max_size=None)
+    precision, recall = precision_recall.compute_pr(opts, max_real=50000, num_gen=50000, nhood_size=3,
+                                                    row_batch_size=10000, col_batch_size=10000)
+    return dict(pr50k3_precision=precision, pr50k3_recall=recall)

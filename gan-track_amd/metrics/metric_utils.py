@@ -4,9 +4,12 @@ Differences by design (same numbers up to float64 summation order):
   * feature moments accumulate ON THE DEVICE in float64 (sum x and x^T x as GEMMs), and ranks combine
     them with ONE all_reduce at the end; the reference broadcasts every batch's features from every rank
     to every rank and accumulates in numpy on the host (:116-126);
-  * the Inception detector is not fetched from NGC (no network, and unpickling a downloaded file runs
-    code): it is SUPPLIED -- `register_detector(url_or_name, module)` with any callable
-    images uint8 [N, 3, H, W] -> features [N, F], or a TorchScript file path.
+  * the detectors (Inception for FID, VGG16 for precision / recall) are not fetched from NGC (no network, and
+    unpickling a downloaded file runs code): they are SUPPLIED -- `register_detector(url_or_name, module)` with any
+    callable images uint8 [N, 3, H, W] -> features [N, F], or a TorchScript file path (SG2_FID_DETECTOR /
+    SG2_PR_DETECTOR);
+  * with capture_all, reduce() leaves the GLOBAL feature set on every rank (one padded all_gather), so every rank
+    computes the same precision / recall; the reference broadcasts every batch.
 
 Kept as in the reference, because they change the numbers:
   * the real-image quirk (:240-246): a batch whose max() is not exactly 255 is multiplied by 255,
@@ -38,14 +41,20 @@ def get_feature_detector_name(url):
     return os.path.splitext(url.split('/')[-1])[0]
 
 
+# Offline detector files by detector name (the url's file name): a TorchScript file named by the variable stands in
+# for that detector only -- the Inception network must never answer a VGG16 request.
+DETECTOR_ENV = {'inception-2015-12-05': 'SG2_FID_DETECTOR', 'vgg16': 'SG2_PR_DETECTOR'}
+
+
 def get_feature_detector(url, device=torch.device('cpu'), num_gpus=1, rank=0, verbose=False):
     det = _detectors.get(url)
     if det is None:
-        path = url if os.path.isfile(url) else os.environ.get('SG2_FID_DETECTOR')
+        var = DETECTOR_ENV.get(get_feature_detector_name(url))
+        path = url if os.path.isfile(url) else (os.environ.get(var) if var is not None else None)
         if path is None or not os.path.isfile(path):
+            hint = f' or point {var} at a TorchScript file' if var is not None else ''
             raise RuntimeError(f'feature detector {url!r} is not available offline: register one with '
-                               'metrics.metric_utils.register_detector() or point SG2_FID_DETECTOR at a '
-                               'TorchScript file')
+                               f'metrics.metric_utils.register_detector(){hint}')
         det = _detectors[url] = torch.jit.load(path, map_location='cpu').eval()
     if isinstance(det, torch.nn.Module):
         det = det.to(device)
@@ -127,10 +136,29 @@ class FeatureStats:
         if num_gpus > 1 and self.capture_mean_cov:
             torch.distributed.all_reduce(self.raw_mean)
             torch.distributed.all_reduce(self.raw_cov)
+        if num_gpus > 1 and self.capture_all:
+            # every rank ends with the global set: the items a single process would have kept, in rank order (the
+            # users are means over the set).  The ranks hold unequal counts after the max_items cut: pad to the
+            # largest count around one all_gather, then trim.
+            dev = self.raw_mean.device
+            local = torch.from_numpy(self.get_all()).to(dev)
+            counts = [torch.zeros([], dtype=torch.int64, device=dev) for _ in range(num_gpus)]
+            torch.distributed.all_gather(counts, torch.tensor(local.shape[0], dtype=torch.int64, device=dev))
+            counts = [int(c) for c in counts]
+            padded = torch.zeros([max(counts), self.num_features], dtype=local.dtype, device=dev)
+            padded[:local.shape[0]] = local
+            parts = [torch.empty_like(padded) for _ in range(num_gpus)]
+            torch.distributed.all_gather(parts, padded)
+            self.all_features = [torch.cat([p[:c] for p, c in zip(parts, counts)]).cpu().numpy()]
 
     def get_all(self):
         assert self.capture_all
+        if not self.all_features:
+            return np.zeros([0, self.num_features], dtype=np.float32)
         return np.concatenate(self.all_features, axis=0)
+
+    def get_all_torch(self):
+        return torch.from_numpy(self.get_all())
 
     def get_mean_cov(self):
         assert self.capture_mean_cov
@@ -139,13 +167,24 @@ class FeatureStats:
         return mean, cov - np.outer(mean, mean)
 
     def save(self, path):
+        # (a capture_all object adds its features and flags; a moments-only file is what it always was)
+        extra = dict(capture_all=1, capture_mean_cov=int(self.capture_mean_cov),
+                     all_features=self.get_all()) if self.capture_all else {}
+        moments = self.capture_mean_cov or not self.capture_all     # (features only: no F x F block of zeros)
+        raw_mean = self.raw_mean.cpu().numpy() if moments else np.zeros([0])
+        raw_cov = self.raw_cov.cpu().numpy() if moments else np.zeros([0, 0])
         np.savez(path, num_items=self.num_items, num_features=self.num_features, max_items=-1 if self.max_items is None
-                 else self.max_items, raw_mean=self.raw_mean.cpu().numpy(), raw_cov=self.raw_cov.cpu().numpy())
+                 else self.max_items, raw_mean=raw_mean, raw_cov=raw_cov, **extra)
 
     @staticmethod
     def load(path):
         z = np.load(path, allow_pickle=False)
-        s = FeatureStats(capture_mean_cov=True, max_items=None if int(z['max_items']) < 0 else int(z['max_items']))
+        max_items = None if int(z['max_items']) < 0 else int(z['max_items'])
+        if 'capture_all' in z.files:
+            s = FeatureStats(capture_all=True, capture_mean_cov=bool(int(z['capture_mean_cov'])), max_items=max_items)
+            s.all_features = [z['all_features']]
+        else:
+            s = FeatureStats(capture_mean_cov=True, max_items=max_items)
         s.num_items, s.num_features = int(z['num_items']), int(z['num_features'])
         s.raw_mean, s.raw_cov = torch.from_numpy(z['raw_mean']), torch.from_numpy(z['raw_cov'])
         return s

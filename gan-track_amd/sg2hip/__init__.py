@@ -85,8 +85,11 @@ SIGNATURES = {
     'sg2_infnorm_vjp_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
     'sg2_pack_weight': [_vp, _i, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i, _f, _vp],
     'sg2_pack_weight_multi': [_vp, _i, _vp],
+    'sg2_knn_scratch_bytes': [_c_i64p, _i64, _i64, _i],
+    'sg2_knn_radii': [_vp, _vp, _i, _i64, _i, _i, _i, _vp, _i64, _vp],
+    'sg2_manifold_member': [_vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp],
 }
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SG2_ABI_VERSION 9
+#define SG2_ABI_VERSION 10
 
 enum sg2_dtype { SG2_F32 = 0, SG2_F16 = 1, SG2_BF16 = 2, SG2_F32S3 = 3 };
 
@@ -394,6 +394,29 @@ int sg2_adam_multi(const int64_t* seg, const float* coef, const int64_t* blocks,
 /* dst = src.lerp(dst, beta) per segment (the G_ema update, training_loop_mi_multimodal.py:363-364);
  * seg [nseg][3] = {float* dst, const float* src, numel}. */
 int sg2_lerp_multi(const int64_t* seg, const int64_t* blocks, int nblocks, float beta, void* stream);
+
+/* k-nearest-neighbour manifolds of the improved precision / recall metric (ABI 10; SG3/metrics/precision_recall.py:
+ * 51-61: cdist in blocks, kthvalue(nhood_size + 1), `dist <= kth`, any).  One fp16 "NT" GEMM whose [rows, cols]
+ * distance matrix is never stored: the epilogue keeps the k + 1 smallest entries (radii) or one flag (membership)
+ * per row.  Arithmetic of both calls:
+ *   d2 = max(|a|^2 + |b|^2 - 2 a.b, 0) in f32 (a.b: fp16 MFMA, f32 accumulation; the squared norms: f32 sums of the
+ *   fp16 values in a fixed order), dist = sqrtf(d2); round16 != 0: dist is rounded to fp16 (nearest even) before it
+ *   is ranked or compared -- the reference's fp16 distance matrix, fp16 radii and fp16 `<=`.
+ * Results are bitwise reproducible (no atomics: per-split partials merged by a second kernel).
+ * dtype: SG2_F16 only; d % 8 == 0; 1 <= k <= 7; each operand below 2 GiB and 16-byte aligned.
+ *
+ * sg2_knn_scratch_bytes: the scratch both calls below need for `rows` rows against `cols` columns (radii:
+ * rows = cols = n; membership: rows = p, cols = n).  A shorter scratch is an argument error.
+ * sg2_knn_radii: radii[i] = the (k + 1)-th smallest of dist(x_i, x_j) over all j < n, the diagonal taken as exactly
+ *   0 and counted (x [n, d] row-major, n >= k + 1).
+ * sg2_manifold_member: hit[i] = 1 if dist(probes_i, manifold_j) <= radii[j] for any j < n, else 0
+ *   (probes [p, d], manifold [n, d], radii [n]; a NaN or negative radius never matches). */
+int sg2_knn_scratch_bytes(int64_t* bytes, int64_t rows, int64_t cols, int k);
+int sg2_knn_radii(float* radii, const void* x, int dtype, int64_t n, int d, int k, int round16, void* scratch,
+                  int64_t scratch_bytes, void* stream);
+int sg2_manifold_member(uint8_t* hit, const void* probes, int64_t p, const void* manifold, int64_t n,
+                        const float* radii, int dtype, int d, int round16, void* scratch, int64_t scratch_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }
