@@ -1,0 +1,158 @@
+"""Project the slices of a dataset into the W space of a trained generator -- the reference's projector CLI
+(SG3/genlib/run_projector_mi_multimodal.py): the same flags and defaults, the same config dict (written to
+training_options.json), run-directory numbering and description string.
+
+    python gan-track_amd/genlib/run_projector_mi_multimodal.py --data=DATA.zip --outdir=reports --gpus=1 \\
+        --experiment=00000 --network_pkl=network-snapshot-005000.pkl
+
+The snapshot is <outdir>/<dataset>/training-runs/<dataset name>/<modalities>/<run containing --experiment>/<--network_pkl>
+(genlib/metric/metric_utils.get_outdir_model_path); an absolute path to an existing file in --network_pkl is taken as
+is.  Results go to <outdir>/<dataset>/projection-runs/<dataset name>/<modalities>/<NNNNN>-<description>/.
+"""
+import json
+import os
+import re
+import sys
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+import click  # noqa: E402
+
+import dnnlib  # noqa: E402
+
+REQUIRED = ('data', 'outdir', 'gpus', 'experiment', 'network_pkl')
+DEFAULTS = dict(modalities='MR_nonrigid_CT,MR_MR_T2', dataset='Pelvis_2.1', split='train', dtype='float32', desc=None,
+                seed=303, snap=50, workers=3, step_patient_slice=2, target_fname=None, num_steps=500, early_stopping=50,
+                w_lpips=1.0, w_pix=1e-4, save_final_projection=True, snap_video=60, snap_optimization_history=60,
+                verbose=False)
+
+
+def init_dataset_mi_multimodal_kwargs(data, dtype, split, modalities):
+    from train_mi_multimodal import init_dataset_kwargs
+    try:
+        return init_dataset_kwargs(data, dtype, split, modalities)
+    except IOError as err:
+        raise click.ClickException(f'--data: {err}')
+
+
+def build_config(**kwargs):
+    """click-flag dict -> (c, desc, outdir, outdir_model)."""
+    opts = dnnlib.EasyDict(DEFAULTS)
+    opts.update({k.replace('-', '_'): v for k, v in kwargs.items() if v is not None})
+    for k in REQUIRED:
+        if opts.get(k) is None:
+            raise click.ClickException(f'--{k} is required')
+    c = dnnlib.EasyDict()
+    c.projector_kwargs = dnnlib.EasyDict()
+    c.training_set_kwargs, dataset_name = init_dataset_mi_multimodal_kwargs(
+        data=opts.data, dtype=opts.dtype, split=opts.split, modalities=opts.modalities)
+    c.num_gpus = opts.gpus
+    c.batch_size = 1
+    c.image_snapshot_ticks = c.network_snapshot_ticks = opts.snap
+    c.random_seed = c.training_set_kwargs.random_seed = opts.seed
+    for k in ('experiment', 'network_pkl', 'step_patient_slice', 'target_fname', 'num_steps', 'early_stopping', 'w_lpips',
+              'w_pix', 'save_final_projection', 'snap_video', 'snap_optimization_history', 'verbose'):
+        c.projector_kwargs[k] = opts[k]
+    for k in ('first_num_steps', 'first_early_stopping'):      # this build's: the cold start's step count / patience
+        if opts.get(k) is not None:
+            c.projector_kwargs[k] = opts[k]
+    mods = ','.join(opts.modalities.replace(' ', '').split(','))
+    outdir_model = os.path.join(opts.outdir, opts.dataset, 'training-runs', f'{dataset_name:s}', f'{mods:s}')
+    outdir = os.path.join(opts.outdir, opts.dataset, 'projection-runs', f'{dataset_name:s}', f'{mods:s}')
+    desc = (f'{dataset_name:s}-split_{opts.split}-stylegan_exp_{opts.experiment}-network_filename_{opts.network_pkl}'
+            f'-w_lips_{opts.w_lpips}-w_pix_{opts.w_pix}')
+    if opts.desc is not None:
+        desc += f'-{opts.desc}'
+    return c, desc, outdir, outdir_model
+
+
+def next_run_dir(outdir, desc):
+    prev = [x for x in os.listdir(outdir) if os.path.isdir(os.path.join(outdir, x))] if os.path.isdir(outdir) else []
+    ids = [int(m.group()) for m in (re.match(r'^\d+', x) for x in prev) if m is not None]
+    return os.path.join(outdir, f'{max(ids, default=-1) + 1:05d}-{desc}')
+
+
+def launch_projection(c, desc, outdir, outdir_model):
+    from genlib.metric import metric_utils
+    from genlib.projector import projection_loop
+    log = dnnlib.util.Logger(should_flush=True)
+    try:
+        c.run_dir = next_run_dir(outdir, desc)
+        assert not os.path.exists(c.run_dir)
+        print('\nTraining options:\n' + json.dumps(c, indent=2) + '\n')
+        for label, value in (('Output directory:', c.run_dir), ('Number of GPUs:', c.num_gpus),
+                             ('Batch size:', f'{c.batch_size} images'), ('Dataset path:', c.training_set_kwargs.path),
+                             ('Dataset dtype:', c.training_set_kwargs.dtype), ('Split:', c.training_set_kwargs.split),
+                             ('Modalities:', c.training_set_kwargs.modalities),
+                             ('Dataset size:', f'{c.training_set_kwargs.max_size} images'),
+                             ('Dataset resolution:', c.training_set_kwargs.resolution),
+                             ('Experiment id for StyleGAN2-ADA', c.projector_kwargs.experiment),
+                             ('Selection step for inversion', c.projector_kwargs.step_patient_slice),
+                             ('Num steps:', c.projector_kwargs.num_steps),
+                             ('Patience for early stopping:', c.projector_kwargs.early_stopping),
+                             ('w_lpips:', c.projector_kwargs.w_lpips), ('w_pix:', c.projector_kwargs.w_pix)):
+            print(f'{label:<36s}{value}')
+        print('\nCreating output directory...')
+        os.makedirs(c.run_dir)
+        with open(os.path.join(c.run_dir, 'training_options.json'), 'wt') as f:
+            json.dump(c, f, indent=2)
+        c.projector_kwargs.outdir_model = metric_utils.get_outdir_model_path(
+            outdir=c.run_dir, outdir_model=outdir_model, experiment=c.projector_kwargs.experiment,
+            metric_name=c.projector_kwargs.network_pkl, modalities=c.training_set_kwargs.modalities,
+            snap=c.network_snapshot_ticks, projector_kwargs=c.projector_kwargs)
+        print('Launching processes...')
+        file_log = dnnlib.util.Logger(file_name=os.path.join(c.run_dir, 'log.txt'), file_mode='a', should_flush=True)
+        try:
+            projection_loop.projection_loop(rank=0, **c)
+        finally:
+            file_log.close()
+    finally:
+        log.close()
+    return c.run_dir
+
+
+@click.command()
+@click.option('--data', help='Target image dataset to project to', metavar='[ZIP|DIR]', type=str, required=True)
+@click.option('--outdir', help='Where to save the results', metavar='DIR', required=True)
+@click.option('--modalities', help='Modalities for StyleGAN', metavar='STRING', type=str, default='MR_nonrigid_CT,MR_MR_T2')
+@click.option('--dataset', help='Dataset name', metavar='STRING', type=str, default='Pelvis_2.1')
+@click.option('--split', help='Validation split', metavar='STRING', type=str, default='train')
+@click.option('--dtype', help='Dynamic range of images', type=str, default='float32')
+@click.option('--desc', help='String to include in result dir name', metavar='STR', type=str)
+@click.option('--gpus', help='Number of GPUs to use', metavar='INT', type=click.IntRange(min=1), required=True)
+@click.option('--seed', help='Random seed', type=int, default=303, show_default=True)
+@click.option('--snap', help='How often to save snapshots', metavar='TICKS', type=click.IntRange(min=1), default=50,
+              show_default=True)
+@click.option('--workers', help='DataLoader worker processes', metavar='INT', type=click.IntRange(min=1), default=3,
+              show_default=True)
+@click.option('--experiment', help='Experiment run id to take from the results', type=str, required=True)
+@click.option('--network_pkl', help='Network pickle filename or Metric filename', type=str, required=True)
+@click.option('--step_patient_slice', help='Selection step for slices to invert in each volume',
+              type=click.IntRange(min=1, max=20), default=2, required=True)
+@click.option('--target_fname', help='Path to image for test experiment', metavar='DIR', default=None, show_default=True)
+@click.option('--num-steps', help='Number of optimization steps', type=int, default=500, show_default=True)
+@click.option('--early_stopping', help='Patience for early stopping', type=click.IntRange(min=1), default=50,
+              show_default=True)
+@click.option('--w_lpips', help='Weight of lpips loss', type=float, default=1.0, show_default=True)
+@click.option('--w_pix', help='Weight of recontruction loss', type=float, default=1e-4, show_default=True)
+@click.option('--save_final_projection', help='Save the final results of each projection', type=bool, default=True,
+              show_default=True)
+@click.option('--snap_video', help='How often to save video snapshots in the patient stack', metavar='TICKS',
+              type=click.IntRange(min=1), default=60, show_default=True)
+@click.option('--snap_optimization_history', help='How often to save loss snapshots in the patient stack',
+              metavar='TICKS', type=click.IntRange(min=1), default=60, show_default=True)
+@click.option('--verbose', help='Save logs of optimization process (mp4 video and loss history)', type=bool,
+              default=False, show_default=True)
+@click.option('--first_num_steps', help='Steps of a patient\'s first (cold) slice (this build; default 1000)',
+              type=click.IntRange(min=1), default=None)
+@click.option('--first_early_stopping', help='Patience of a patient\'s first slice (this build; default 100000)',
+              type=click.IntRange(min=1), default=None)
+def main(**kwargs):
+    c, desc, outdir, outdir_model = build_config(**kwargs)
+    launch_projection(c=c, desc=desc, outdir=outdir, outdir_model=outdir_model)
+
+
+if __name__ == '__main__':
+    main()   # pylint: disable=no-value-for-parameter

@@ -7,7 +7,7 @@ Differences by design (same numbers up to float64 summation order):
   * the detectors (Inception for FID, VGG16 for precision / recall) are not fetched from NGC (no network, and
     unpickling a downloaded file runs code): they are SUPPLIED -- `register_detector(url_or_name, module)` with any
     callable images uint8 [N, 3, H, W] -> features [N, F], or a TorchScript file path (SG2_FID_DETECTOR /
-    SG2_PR_DETECTOR);
+    SG2_PR_DETECTOR; SG2_LPIPS_DETECTOR for the projector's LPIPS network);
   * with capture_all, reduce() leaves the GLOBAL feature set on every rank (one padded all_gather), so every rank
     computes the same precision / recall; the reference broadcasts every batch.
 
@@ -42,17 +42,28 @@ def get_feature_detector_name(url):
 
 
 # Offline detector files by detector name (the url's file name): a TorchScript file named by the variable stands in
-# for that detector only -- the Inception network must never answer a VGG16 request.
-DETECTOR_ENV = {'inception-2015-12-05': 'SG2_FID_DETECTOR', 'vgg16': 'SG2_PR_DETECTOR'}
+# for that detector only -- the Inception network must never answer a VGG16 request.  A key with an extension is the
+# url's whole file name and goes first: the projector's LPIPS network (".../metrics/vgg16.pt", called with
+# return_lpips=True) has a variable of its own and falls back to the precision / recall one (NVIDIA ships the VGG16 both
+# ways; whether the two files hold the same scripted network is not verified here), while what FID and pr50k3 get
+# (".../inception-2015-12-05.pkl", ".../vgg16.pkl") is unchanged.
+DETECTOR_ENV = {'inception-2015-12-05': 'SG2_FID_DETECTOR', 'vgg16': 'SG2_PR_DETECTOR',
+                'vgg16.pt': ('SG2_LPIPS_DETECTOR', 'SG2_PR_DETECTOR')}
+
+
+def detector_env_vars(url):
+    """The environment variables that may name an offline file for `url`, in order of preference."""
+    var = DETECTOR_ENV.get(url.split('/')[-1], DETECTOR_ENV.get(get_feature_detector_name(url)))
+    return () if var is None else ((var,) if isinstance(var, str) else tuple(var))
 
 
 def get_feature_detector(url, device=torch.device('cpu'), num_gpus=1, rank=0, verbose=False):
     det = _detectors.get(url)
     if det is None:
-        var = DETECTOR_ENV.get(get_feature_detector_name(url))
-        path = url if os.path.isfile(url) else (os.environ.get(var) if var is not None else None)
+        names = detector_env_vars(url)
+        path = url if os.path.isfile(url) else next((os.environ[v] for v in names if os.environ.get(v)), None)
         if path is None or not os.path.isfile(path):
-            hint = f' or point {var} at a TorchScript file' if var is not None else ''
+            hint = f' or point {" or ".join(names)} at a TorchScript file' if names else ''
             raise RuntimeError(f'feature detector {url!r} is not available offline: register one with '
                                f'metrics.metric_utils.register_detector(){hint}')
         det = _detectors[url] = torch.jit.load(path, map_location='cpu').eval()

@@ -88,8 +88,12 @@ SIGNATURES = {
     'sg2_knn_scratch_bytes': [_c_i64p, _i64, _i64, _i],
     'sg2_knn_radii': [_vp, _vp, _i, _i64, _i, _i, _i, _vp, _i64, _vp],
     'sg2_manifold_member': [_vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp],
+    'sg2_noise_reg_scratch_bytes': [_c_i64p, _c_i64p, _i],
+    'sg2_noise_reg_fwd': [_vp, _vp, _vp, _c_i64p, _i, _vp, _vp],
+    'sg2_noise_reg_bwd': [_vp, _vp, _vp, _vp, _c_i64p, _i, _vp, _i, _vp],
+    'sg2_noise_normalize_multi': [_vp, _c_i64p, _i, _vp],
 }
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 

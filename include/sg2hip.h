@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SG2_ABI_VERSION 10
+#define SG2_ABI_VERSION 11
 
 enum sg2_dtype { SG2_F32 = 0, SG2_F16 = 1, SG2_BF16 = 2, SG2_F32S3 = 3 };
 
@@ -417,6 +417,28 @@ int sg2_knn_radii(float* radii, const void* x, int dtype, int64_t n, int d, int 
 int sg2_manifold_member(uint8_t* hit, const void* probes, int64_t p, const void* manifold, int64_t n,
                         const float* radii, int dtype, int d, int round16, void* scratch, int64_t scratch_bytes,
                         void* stream);
+
+/* The small-tensor part of a latent projection step (ABI 11; SG3/genlib/projector/projector.py:259-268 the noise
+ * regulariser, :294-298 the per-buffer renormalisation).  All noise buffers of a generator live in ONE flat f32 device
+ * buffer; `table` is a HOST array int64 [nbuf][2] of (offset of the buffer in flat, in floats; R) rows, 1 <= nbuf <= 32.
+ * R is a power of two in 4..1024 (square buffers), every offset a multiple of 4 floats, flat 16-byte aligned; anything
+ * else is an argument error and no device work is issued.  A buffer's levels: evaluate at the current size, stop if the
+ * size is <= 8, else 2x2 average-pool and repeat (R <= 8: one level, 16: two, 256: six).
+ * No atomics: every sum is a fixed tree (serial runs of <= 16 terms), so results are bitwise reproducible.
+ *
+ * sg2_noise_reg_scratch_bytes: the scratch (pooled levels + per-chunk partial sums) the two calls below need.
+ * sg2_noise_reg_fwd (3 launches): reg[0] = sum_buf sum_level mean(n roll_x n)^2 + mean(n roll_y n)^2 (circular shifts by
+ *   one); means [sum of levels][2] = the (x, y) means, buffers in table order, levels from the finest.
+ * sg2_noise_reg_bwd (1 launch): gflat[off + i] (+)= greg[0] * sum_level 4^-l (2 mx_l / cnt_l (W + E) + 2 my_l / cnt_l
+ *   (N + S)) of element i's level-l ancestor's circular neighbours; `flat`, `means` and `scratch` as the forward call
+ *   left them; greg: device scalar; accumulate != 0 adds into gflat, 0 assigns every element of every buffer.
+ * sg2_noise_normalize_multi (1 launch): per buffer, in place, x -= mean(x); x *= 1 / sqrt(mean(x^2)). */
+int sg2_noise_reg_scratch_bytes(int64_t* bytes, const int64_t* table, int nbuf);
+int sg2_noise_reg_fwd(float* reg, float* means, const float* flat, const int64_t* table, int nbuf, void* scratch,
+                      void* stream);
+int sg2_noise_reg_bwd(float* gflat, const float* greg, const float* means, const float* flat, const int64_t* table,
+                      int nbuf, const void* scratch, int accumulate, void* stream);
+int sg2_noise_normalize_multi(float* flat, const int64_t* table, int nbuf, void* stream);
 
 #ifdef __cplusplus
 }
