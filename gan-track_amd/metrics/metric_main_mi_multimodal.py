@@ -3,7 +3,7 @@ keeps the reference's entry points (register_metric, is_valid_metric, list_valid
 report_metric) and its output contract (one JSON line per evaluation appended to
 <run_dir>/metric-<modality>-<metric>.jsonl); the FID metrics are the two the Claro / Pelvis runs name, the
 precision / recall metrics (pr50k3_full, pr50k3) the one further metric the reference adapted to its per-modality
-evaluation."""
+evaluation, and ppl2_wend the perceptual path length its offline evaluation (calc_metrics_mi_multimodal.py) names."""
 import json
 import os
 import time
@@ -14,6 +14,7 @@ import dnnlib
 from . import metric_utils
 from . import frechet_inception_distance
 from . import precision_recall
+from . import perceptual_path_length
 
 
 class _Registry:
@@ -117,3 +118,11 @@ def pr50k3(opts):
     precision, recall = precision_recall.compute_pr(opts, max_real=50000, num_gen=50000, nhood_size=3,
                                                     row_batch_size=10000, col_batch_size=10000)
     return dict(pr50k3_precision=precision, pr50k3_recall=recall)
+
+
+@register_metric
+def ppl2_wend(opts):
+    """Perceptual path length in W, path endpoints, full image (:108-111)."""
+    ppl = perceptual_path_length.compute_ppl(opts, num_samples=50000, epsilon=1e-4, space='w', sampling='end',
+                                             crop=False, batch_size=2)
+    return dict(ppl2_wend=ppl)

@@ -92,6 +92,10 @@ SIGNATURES = {
     'sg2_noise_reg_fwd': [_vp, _vp, _vp, _c_i64p, _i, _vp, _vp],
     'sg2_noise_reg_bwd': [_vp, _vp, _vp, _vp, _c_i64p, _i, _vp, _i, _vp],
     'sg2_noise_normalize_multi': [_vp, _c_i64p, _i, _vp],
+    # (additive to ABI 11: the perceptual-path-length passes, csrc/ppl.hip)
+    'sg2_ppl_prep': [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    'sg2_lpips_pair_dist_scratch_bytes': [_c_i64p, _i64, _i64],
+    'sg2_lpips_pair_dist': [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _i64, _vp],
 }
 ABI_VERSION = 11
 

@@ -440,6 +440,29 @@ int sg2_noise_reg_bwd(float* gflat, const float* greg, const float* means, const
                       int nbuf, const void* scratch, int accumulate, void* stream);
 int sg2_noise_normalize_multi(float* flat, const int64_t* table, int nbuf, void* stream);
 
+/* The two streaming passes of a perceptual-path-length sampler call (SG3/metrics/perceptual_path_length.py:71-89).
+ * ADDITIVE entry points: SG2_ABI_VERSION stays 11 -- nothing that existed changes, and a caller built against the
+ * ABI-11 header keeps working; callers that need them look the symbols up.
+ *
+ * sg2_ppl_prep (1 launch): the detector's input from the generator's output.  img f32 NCHW contiguous [N, C, H, W];
+ *   crop != 0: with c = H / 8 the window rows 3c..7c, columns 2c..6c (needs H == W, H % 8 == 0); factor >= 1 divides the
+ *   (cropped) height and width; channel = one source channel, written to all three output channels, or -1 = all
+ *   channels (C = 3: as they are; C = 1: repeated; any other C is an argument error).
+ *   out f32 NCHW [N, 3, H' / factor, W' / factor] = (mean over factor x factor of x + 1) * 127.5 -- an add and a multiply,
+ *   two roundings, never an FMA: at factor 1 bitwise the f32 torch composition (x + 1) * (255 / 2).
+ * sg2_lpips_pair_dist (2 launches): feats f32 [2B, F] row-contiguous (rows 0..B-1 against rows B..2B-1),
+ *   dist[b] = (sum_j (feats[b][j] - feats[B + b][j])^2) / (float)(eps * eps), f32 arithmetic, no atomics: a fixed tree
+ *   whose shape depends on F only (serial runs of 8 and of ceil(ceil(F / 8192) / 256) terms, tree depth 18; csrc/ppl.hip),
+ *   so results are bitwise reproducible and a pair gives the same bits alone or in a batch.  Any F; rows that are not
+ *   16-byte aligned are read element by element on the same tree.  1 <= B <= 65535, eps > 0.
+ * sg2_lpips_pair_dist_scratch_bytes: the scratch (one partial sum per 8192-element chunk and pair) the call needs; a
+ *   shorter scratch is an argument error. */
+int sg2_ppl_prep(float* out, const float* img, int N, int C, int H, int W, int channel, int crop, int factor,
+                 void* stream);
+int sg2_lpips_pair_dist_scratch_bytes(int64_t* bytes, int64_t B, int64_t F);
+int sg2_lpips_pair_dist(float* dist, const float* feats, int64_t B, int64_t F, double eps, void* scratch,
+                        int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
