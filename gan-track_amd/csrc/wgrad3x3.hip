@@ -3,6 +3,9 @@
 //
 //   dw[a][ky][kx][b] = sum_{n,oy,ox} g[n,oy,ox,a] u[n,a] * x[n, oy*S + ky - P, ox*S + kx - P, b] s[n,b]
 //   (u = g_scale, s = x_scale: a layer's modulation, optional)
+// Rounding of the scaled operands (pinned by test_wgrad3x3_halo / test_wgrad_halo_phases): the
+// register-staged kernels of every stride write round(x * s) to LDS, s left in f32 (scale8: the f32 product rounded
+// to T); the LDS-DMA kernel keeps x * s in f32 (it scales its partial sums).
 //
 // Split by output phase: with S = 2, tap k reads x at (o + shift) * S + phase where
 // (k - P) = shift * S + phase; for one phase the taps' shifts lie in {-1, 0, 1}.  So each phase is a

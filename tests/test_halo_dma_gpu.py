@@ -12,6 +12,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import elementwise as EW
 from golden_util import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -110,3 +111,32 @@ def test_halo_dma_matches_register_route_and_float64(shape, dtype, monkeypatch):
     for form in ('dgrad_atomic', 'dgrad_det'):
         check(new[form][0], c0 * d[:, :, None, None], form)
         assert rel_err(new[form][2], dot_ref) < tol, form
+
+    # 4. every element of the new route's outputs (tests/elementwise.py).  Rounding model: round(x round(s)) -- the
+    # LDS-DMA form scales the staged halo in place by the style rounded to the activation type, and so does the
+    # register-staged kernel that keeps the two shapes the gate refuses; bias rounded to the activation type; y_raw
+    # the accumulator rounded once.  (The old route's outputs are bitwise equal to these, by 1.)
+    f32 = lambda v: float(np.float32(v))
+    K = 9 * Cin
+    sl0 = EW.accumulation_slack(K, F.conv2d(x.to(dtype).double().abs(), wd.abs(), padding=1))
+    xm = EW.mod_x(x, s, dtype)
+    cx = F.conv2d(xm, wd, padding=1)
+    slx = EW.accumulation_slack(K, F.conv2d(xm.abs(), wd.abs(), padding=1))
+    dd = d[:, :, None, None].double()
+    ng = noise.to(dtype).double() * f32(0.3)
+
+    def epi32(z):    # the scalar arguments at the f32 values the kernel receives
+        return (F.leaky_relu(z, f32(0.2)) * f32(np.sqrt(2))).clamp(-1.5, 1.5)
+
+    def ew(got, ref, slack, what):
+        print(f'elementwise halo_dma {what} {str(dtype)[6:]}: worst error / bound '
+              f'{EW.assert_elementwise(got, ref, slack, dtype, what):.3f}')
+
+    ew(new['plain'], c0, sl0, 'plain')
+    ew(new['dblock'][0], epi32(c0 + bd), EW.epilogue_slack(sl0, c0, b=bd, gain=f32(np.sqrt(2)), alpha=f32(0.2)), 'dblock y')
+    ew(new['dblock'][1], c0, sl0, 'dblock raw')
+    ew(new['glayer'][0], epi32(cx * dd + ng + bd),
+       EW.epilogue_slack(slx, cx, dd, ng, bd, gain=f32(np.sqrt(2)), alpha=f32(0.2)), 'glayer y')
+    ew(new['glayer'][1], cx, slx, 'glayer raw')
+    for form in ('dgrad_atomic', 'dgrad_det'):
+        ew(new[form][0], c0 * dd, EW.epilogue_slack(sl0, c0, dd), form + ' out_scale')

@@ -1,15 +1,21 @@
 """Parity of the HIP ops (called through the C-ABI via the product wrappers) against the CPU oracle,
 the reference's golden vectors, and torch-fp32 references for the convolution kernels.
 
-Tolerances (relative L2 error):
-  fp32 elementwise / FIR / grid_sample: 1e-5     fp32 MFMA convolutions: 1e-5
-  fp16/bf16 (fp32 accumulate) vs the fp32 reference: 1e-2 (fp16), 2e-2 (bf16)
+Tolerances (relative L2 error, golden_util.rel_err):
+  fp32 elementwise / FIR / grid_sample: 1e-5     fp32 convolutions: 1e-5 (outputs), 1e-4 (some gradients)
+  16-bit (f32 accumulate) against float64 of the same rounded operands:
+    3x3 / up-2 / stride-2 convolutions 5e-3 (fp16), 2e-2 (bf16); generic implicit GEMM 4e-3 / 2e-2;
+    FIR and weight gradients 2e-3 / 1e-2; layer-level fused-against-composed comparisons 1e-2 / 4e-2
+Beside them every 16-bit conv / FIR / wgrad / layer_bwd output is bounded element by element (tests/elementwise.py:
+|y - ref| <= u |ref| + (1 + u) slack + tiny, no element exempt), against a float64 reference that rounds where the
+route under test rounds; each such case names its one rounding model.
 """
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import elementwise as EW
 from golden_util import load, lit, rel_err
 from rngtape import Tape
 from oracle import sg2_oracle as O
@@ -132,6 +138,8 @@ def test_upfirdn2d_vec_path(dtype):
         y = upfirdn2d.upfirdn2d(xd, f.to(DEV), **kw)
         r = O.upfirdn2d(x.to(dtype).float(), f, **kw)
         assert rel_err(y.float(), r) < tol, kw
+        if dtype != torch.float32:      # one pass over the 2-D filter, K = 16 taps (tests/elementwise.py fir_ref)
+            _elementwise(y, *EW.fir_ref(x, f, dtype, **kw), dtype, f'fir vec {kw}')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
@@ -151,11 +159,18 @@ def test_upfirdn2d_f4s_c32(dtype, monkeypatch):
         r = O.upfirdn2d(x, f, padding=pad, gain=4)
         assert y.shape == r.shape
         assert rel_err(y.float(), r) < tol, (n, h, w, pad)
+        rm, sl = EW.fir_ref(x, f, dtype, padding=pad, gain=4)
+        _elementwise(y, rm, sl, dtype, 'fir f4s c32')
         f2 = f.to(DEV)                                 # (setup_filter makes the 4-tap filter 2-D)
         s = (torch.rand(n, 32) + 0.5).to(DEV)
         b = (torch.randn(32) * 0.1).to(DEV)
         ye, _ = upfirdn2d.fir_fused(xd, f2, pad, gain=4.0, out_scale=s, bias=b, act=1, alpha=0.2,
                                     act_gain=2 ** 0.5, clamp=256.0)
+        # the fused epilogue: clamp(lrelu(c s + round(b)) sqrt(2), 256), the bias rounded to the activation type
+        f32 = lambda v: float(np.float32(v))
+        sd, bd = s.double().cpu()[:, :, None, None], EW.bias_rounded(b.cpu(), dtype)
+        _elementwise(ye, (F.leaky_relu(rm * sd + bd, f32(0.2)) * f32(2 ** 0.5)).clamp(-256, 256),
+                     EW.epilogue_slack(sl, rm, sd, 0.0, bd, f32(2 ** 0.5), f32(0.2)), dtype, 'fir f4s c32 epilogue')
         monkeypatch.setenv('SG2_FIR_C32', '0')
         assert torch.equal(y, upfirdn2d.upfirdn2d(xd, f.to(DEV), padding=pad, gain=4)), (n, h, w, pad)
         ye2, _ = upfirdn2d.fir_fused(xd, f2, pad, gain=4.0, out_scale=s, bias=b, act=1, alpha=0.2,
@@ -173,6 +188,7 @@ def test_upfirdn2d_up2_blocks(dtype, monkeypatch):
     from torch_utils.ops import upfirdn2d
     torch.manual_seed(5)
     tol = {torch.float32: 1e-5, torch.float16: 2e-3, torch.bfloat16: 1e-2}[dtype]
+    worst = 0.0
     for fk in ([1, 3, 3, 1], [1, 2, 5, 3]):
         f = upfirdn2d.setup_filter(fk)
         for (n, c, h, w) in [(2, 64, 17, 17), (1, 32, 16, 9), (3, 128, 8, 8)]:
@@ -184,10 +200,16 @@ def test_upfirdn2d_up2_blocks(dtype, monkeypatch):
                     r = O.upfirdn2d(x, f, up=2, padding=pad, flip_filter=flip, gain=4)
                     assert y.shape == r.shape
                     assert rel_err(y.float(), r) < tol, (fk, n, c, h, w, pad, flip)
+                    if dtype != torch.float32:
+                        worst = max(worst, EW.assert_elementwise(
+                            y, *EW.fir_ref(x, f, dtype, up=2, padding=pad, flip_filter=flip, gain=4), dtype,
+                            f'fir up2 {(fk, n, c, h, w, pad, flip)}'))
                     monkeypatch.setenv('SG2_UPF_UP2_OFF', '1')
                     y2 = upfirdn2d.upfirdn2d(xd, f.to(DEV), up=2, padding=pad, flip_filter=flip, gain=4)
                     monkeypatch.delenv('SG2_UPF_UP2_OFF')
                     assert torch.equal(y, y2), (fk, n, c, h, w, pad, flip)
+    if dtype != torch.float32:
+        print(f'elementwise fir up2 {str(dtype)[6:]}: worst error / bound {worst:.3f}')
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.float16, torch.bfloat16])
@@ -205,6 +227,9 @@ def test_fir_strip_ragged(dtype):
         ref = O.upfirdn2d(x, f, padding=pad, gain=4)
         y = upfirdn2d.upfirdn2d(xd, f.to(DEV), padding=pad, gain=4)
         assert rel_err(y.float(), ref) < tol, (n, c, h, w, pad)
+        if dtype != torch.float32:
+            rm, sl = EW.fir_ref(x, f, dtype, padding=pad, gain=4)
+            _elementwise(y, rm, sl, dtype, f'fir strip {(n, c, h, w)}')
         oh, ow = ref.shape[2:]
         os_ = torch.rand(n, c) + 0.5
         noise = torch.randn(n, 1, oh, ow).to(dtype).float()
@@ -217,6 +242,15 @@ def test_fir_strip_ragged(dtype):
             z = (torch.where(z > 0, z, z * 0.2) * 1.4).clamp(-2.5, 2.5)
             assert rel_err(yd.float(), z) < tol, (n, c, h, w, pad, aux_mode)
             assert rel_err(aux.float(), ref if aux_mode == 1 else z) < tol, (n, c, h, w, pad, aux_mode)
+            if dtype != torch.float32:      # bias and noise are 16-bit values here; scalars at their f32 values
+                f32 = lambda v: float(np.float32(v))
+                sd, ng, bd = os_.double()[:, :, None, None], noise.double() * f32(0.3), bias.double()[None, :, None, None]
+                zm = rm * sd + ng + bd
+                zm = (torch.where(zm > 0, zm, zm * f32(0.2)) * f32(1.4)).clamp(-2.5, 2.5)
+                zsl = EW.epilogue_slack(sl, rm, sd, ng, bd, f32(1.4), f32(0.2))
+                _elementwise(yd, zm, zsl, dtype, f'fir strip {(n, c, h, w)} epilogue aux_mode {aux_mode}')
+                _elementwise(aux, *((rm, sl) if aux_mode == 1 else (zm, zsl)), dtype,
+                             f'fir strip {(n, c, h, w)} aux {aux_mode}')
 
 
 # ------------------------------------------------------------------ convolutions (torch fp32 reference)
@@ -270,6 +304,14 @@ def test_conv2d_fwd_bwd(case, dtype):
     gxr, gwr = torch.autograd.grad(F.conv2d(xr, wr, stride=s, padding=p), [xr, wr], dy.to(dtype).double())
     assert rel_err(gx.float(), gxr) < tol
     assert rel_err(gw.float(), gwr) < tol * 2
+    if dtype != torch.float32:
+        # elementwise, 16-bit: exact products, f32 accumulation, one rounding; an output sums k k Cin products, an
+        # input gradient at most k k Cout (the taps that reach it)
+        xa, wa, da = xr.detach().abs(), wr.detach().abs(), dy.to(dtype).double().abs()
+        _elementwise(y, yr, EW.accumulation_slack(k * k * Cin, F.conv2d(xa, wa, stride=s, padding=p)), dtype,
+                     f'conv2d {k}x{k} s{s} y')
+        ga = torch.autograd.grad(F.conv2d(xa.requires_grad_(True), wa, stride=s, padding=p), [xa], da)[0]
+        _elementwise(gx, gxr, EW.accumulation_slack(k * k * Cout, ga), dtype, f'conv2d {k}x{k} s{s} dx')
 
 
 @pytest.mark.parametrize('case', [(2, 64, 8, 8, 64, 3, 2, 0), (2, 16, 5, 5, 8, 3, 2, 1), (2, 32, 4, 4, 32, 1, 1, 0),
@@ -294,6 +336,14 @@ def test_conv_transpose2d(case, dtype):
     gxr, gwr = torch.autograd.grad(yr, [xr, wr], dy.to(dtype).double())
     assert rel_err(gx.float(), gxr) < tol
     assert rel_err(gw.float(), gwr) < tol * 2
+    if dtype != torch.float32:
+        # elementwise, 16-bit: an output sums at most k k Cin products (the taps that reach it), an input gradient
+        # k k Cout
+        xa, wa, da = xr.detach().abs(), wr.detach().abs(), dy.to(dtype).double().abs()
+        _elementwise(y, yr.detach(), EW.accumulation_slack(k * k * Cin, F.conv_transpose2d(xa, wa, stride=s, padding=p)),
+                     dtype, f'conv_transpose2d {k}x{k} s{s} y')
+        ga = torch.autograd.grad(F.conv_transpose2d(xa.requires_grad_(True), wa, stride=s, padding=p), [xa], da)[0]
+        _elementwise(gx, gxr, EW.accumulation_slack(k * k * Cout, ga), dtype, f'conv_transpose2d {k}x{k} s{s} dx')
 
 
 def test_conv_double_backward():
@@ -463,20 +513,98 @@ def test_augment_geometric_fused_matches_torch_algebra(p, n, monkeypatch):
 
 
 # ------------------------------------------------------------------ LDS-halo 3x3 conv with fused epilogue
+# The stride-1 3x3 tests share their operands and float64 references (tests/elementwise.py): one convolution and its
+# |.| twin per (seed, shape, dtype, rounding model), kept while one test function's cases run (the ring tests repeat
+# each shape for 36 form x ring cases) and dropped when the next function asks.
+#
+# Rounding models (conv3x3.hip dispatch()) -- every case names ONE:
+#   'plain'   no modulation
+#   'x'       round(x round(s)): the register-staged halo kernel, its LDS-DMA form, the persistent c64p kernel
+#   'w'       per-sample round(W round(s)): the C = 64 ring forms and the C = 32 ring
+#   'legacy'  round(x s) with s left in f32: no stride-1 3x3 route computes it (conv.hip's kernels and the
+#             register-staged weight gradients do: 'x_f32s' in their tests); the L2 assertions written before the
+#             elementwise ones keep it as their reference (its distance from 'x' / 'w' fits the L2 tolerance)
+_C3 = {'owner': None, 'memo': {}}
+C3_GAIN, C3_ALPHA, C3_CLAMP, C3_NG = np.sqrt(2), 0.2, 1.5, 0.3
+
+
+def _c3_memo(owner, key, make):
+    if _C3['owner'] != owner:
+        _C3['owner'] = owner
+        _C3['memo'].clear()
+    if key not in _C3['memo']:
+        _C3['memo'][key] = make()
+    return _C3['memo'][key]
+
+
+def _c3_inputs(owner, seed, shape):
+    """x, w, s, d, noise, b (CPU f32), drawn in this order from torch.manual_seed(seed)."""
+    def make():
+        N, Cin, H, W, Cout = shape
+        torch.manual_seed(seed)
+        return dict(x=torch.randn(N, Cin, H, W), w=torch.randn(Cout, Cin, 3, 3) / np.sqrt(Cin * 9),
+                    s=torch.rand(N, Cin) + 0.5, d=torch.rand(N, Cout) + 0.5, noise=torch.randn(N, 1, H, W),
+                    b=torch.randn(Cout) * 0.1)
+    return _c3_memo(owner, ('in', seed, shape), make)
+
+
+def _c3_ref(owner, seed, shape, dtype, model):
+    """(c, slack_c): the float64 3x3 / pad 1 convolution under a rounding model and the f32 accumulation's slack
+    2 K 2^-24 conv(|x|, |w|), K = 9 Cin ('legacy': slack None)."""
+    def make():
+        t = _c3_inputs(owner, seed, shape)
+        Cin = shape[1]
+        wd = t['w'].to(dtype).double()
+        if model == 'w':
+            wn, xd = EW.mod_w(t['w'], t['s'], dtype), t['x'].to(dtype).double()
+            return (EW.conv_per_sample(xd, wn, padding=1),
+                    EW.accumulation_slack(9 * Cin, EW.conv_per_sample(xd.abs(), wn.abs(), padding=1)))
+        if model == 'legacy':
+            xs = (t['x'].to(dtype).float() * t['s'][:, :, None, None]).to(dtype).double()
+            return F.conv2d(xs, wd, padding=1), None
+        xd = EW.mod_x(t['x'], t['s'], dtype) if model == 'x' else t['x'].to(dtype).double()
+        assert model in ('x', 'plain')
+        return F.conv2d(xd, wd, padding=1), EW.accumulation_slack(9 * Cin, F.conv2d(xd.abs(), wd.abs(), padding=1))
+    return _c3_memo(owner, ('ref', seed, shape, dtype, model), make)
+
+
+def _c3_epilogue(t, c, slack, dtype, demod=False, noise=False, bias=True, gain=C3_GAIN, clamp=C3_CLAMP):
+    """(ref, slack) of clamp(lrelu(c d + noise 0.3 + round(b), 0.2) gain, clamp): the bias rounded to the activation
+    type (conv3x3.hip `(float)(T)a.bias[oc]`), the noise a 16-bit tensor, the scalar arguments at the f32 values
+    the kernels receive."""
+    f32 = lambda v: float(np.float32(v))
+    d = t['d'][:, :, None, None].double() if demod else torch.ones((), dtype=torch.float64)
+    ng = t['noise'].to(dtype).double() * f32(C3_NG) if noise else torch.zeros((), dtype=torch.float64)
+    b = EW.bias_rounded(t['b'], dtype) if bias else torch.zeros((), dtype=torch.float64)
+    ref = (F.leaky_relu(c * d + ng + b, f32(C3_ALPHA)) * f32(gain)).clamp(-clamp, clamp)
+    return ref, EW.epilogue_slack(slack, c, d, ng, b, f32(gain), f32(C3_ALPHA))
+
+
+def _conv_ref(x, w, K, conv=F.conv2d, **kw):
+    """(c, slack) of a float64 convolution of operands already rounded (float64 tensors), K products per element."""
+    return conv(x, w, **kw), EW.accumulation_slack(K, conv(x.abs(), w.abs(), **kw))
+
+
+def _elementwise(got, ref, slack, dtype, what):
+    ratio = EW.assert_elementwise(got, ref, slack, dtype, what)
+    print(f'elementwise {what} {str(dtype)[6:]}: worst error / bound {ratio:.3g}')
+    return ratio
+
+
 @pytest.mark.parametrize('shape', [(2, 64, 32, 32, 64), (2, 64, 20, 37, 96), (1, 512, 32, 32, 512), (2, 128, 16, 16, 128),
                                    (2, 40, 16, 24, 8),
                                    (4, 64, 256, 256, 64), (9, 64, 128, 256, 64)])   # persistent c64 kernel
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
 def test_conv3x3_fused(shape, dtype):
+    """The modulated layer with the full epilogue and its raw output on the route the dispatcher picks for each shape:
+    the two C = 64 shapes of >= 2 tiles per workgroup slot take the ring kernel (form 49; the persistent c64p kernel
+    served them before it), whose modulation rounds on the weight side; every other shape here takes the halo kernel
+    (LDS-DMA or register-staged), which rounds round(x round(s))."""
     from torch_utils.ops import conv2d_gradfix as cg
     N, Cin, H, W, Cout = shape
-    torch.manual_seed(5)
-    x = torch.randn(N, Cin, H, W)
-    w = torch.randn(Cout, Cin, 3, 3) / np.sqrt(Cin * 9)
-    s = torch.rand(N, Cin) + 0.5
-    d = torch.rand(N, Cout) + 0.5
-    noise = torch.randn(N, 1, H, W)
-    b = torch.randn(Cout) * 0.1
+    model = 'w' if shape in ((4, 64, 256, 256, 64), (9, 64, 128, 256, 64)) else 'x'
+    t = _c3_inputs('fused', 5, shape)
+    x, w, s, d, noise, b = (t[k] for k in ('x', 'w', 's', 'd', 'noise', 'b'))
     xd = x.to(DEV, dtype).contiguous(memory_format=torch.channels_last)
     wp = cg._pack_conv(w.to(DEV, dtype))
     y, raw = cg.conv3x3_fused(xd, wp, Cout, in_scale=s.to(DEV), out_scale=d.to(DEV),
@@ -489,6 +617,9 @@ def test_conv3x3_fused(shape, dtype):
     tol = 5e-3 if dtype == torch.float16 else 2e-2
     assert rel_err(raw.float(), c) < tol
     assert rel_err(y.float(), yr) < tol
+    cm, sl = _c3_ref('fused', 5, shape, dtype, model)
+    _elementwise(raw, cm, sl, dtype, f'fused[{model}] raw')
+    _elementwise(y, *_c3_epilogue(t, cm, sl, dtype, demod=True, noise=True), dtype, f'fused[{model}] y')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
@@ -505,34 +636,35 @@ def test_conv3x3_halo_direct(dtype, shape, direct, monkeypatch):
     monkeypatch.setenv('SG2_HALO_DIRECT', direct)
     monkeypatch.setenv('SG2_C64_RING', '0')
     N, Cin, H, W, Cout = shape
-    torch.manual_seed(13)
-    x = torch.randn(N, Cin, H, W)
-    w = torch.randn(Cout, Cin, 3, 3) / np.sqrt(Cin * 9)
-    s = torch.rand(N, Cin) + 0.5
-    d = torch.rand(N, Cout) + 0.5
-    noise = torch.randn(N, 1, H, W)
-    b = torch.randn(Cout) * 0.1
+    t = _c3_inputs('halo_direct', 13, shape)
+    x, w, s, d, noise, b = (t[k] for k in ('x', 'w', 's', 'd', 'noise', 'b'))
     xd = x.to(DEV, dtype).contiguous(memory_format=torch.channels_last)
     wp = cg._pack_conv(w.to(DEV, dtype))
     y, raw = cg.conv3x3_fused(xd, wp, Cout, in_scale=s.to(DEV), out_scale=d.to(DEV),
                               noise=noise.to(DEV, dtype).reshape(N, H, W).contiguous(), noise_gain=0.3,
                               bias=b.to(DEV), act=1, alpha=0.2, gain=np.sqrt(2), clamp=1.5, want_raw=True)
-    xs = (x.to(dtype).float() * s[:, :, None, None]).to(dtype).double()
-    c = F.conv2d(xs, w.to(dtype).double(), padding=1)
+    c, _ = _c3_ref('halo_direct', 13, shape, dtype, 'legacy')
     z = c * d[:, :, None, None] + noise.to(dtype).double() * 0.3 + b[None, :, None, None]
     yr = (F.leaky_relu(z, 0.2) * np.sqrt(2)).clamp(-1.5, 1.5)
     tol = 5e-3 if dtype == torch.float16 else 2e-2
     assert rel_err(raw.float(), c) < tol and rel_err(y.float(), yr) < tol
     for n in range(N):
         assert rel_err(y[n].float(), yr[n]) < 2 * tol, n
-    src = torch.randn(N, Cout, H, W).to(dtype)
-    c0 = F.conv2d(x.to(dtype).double(), w.to(dtype).double(), padding=1)
+    # elementwise, model 'x': no shape here is C = 64 -> 64, so with either epilogue the route is a halo kernel
+    # (direct '1': the LDS-DMA form where W >= 32, the register-staged one at 16 x 16; '0': register-staged)
+    cm, sl = _c3_ref('halo_direct', 13, shape, dtype, 'x')
+    _elementwise(raw, cm, sl, dtype, f'halo direct={direct} raw')
+    _elementwise(y, *_c3_epilogue(t, cm, sl, dtype, demod=True, noise=True), dtype, f'halo direct={direct} y')
+    src = torch.randn(N, Cout, H, W, generator=torch.Generator().manual_seed(14)).to(dtype)
+    c0, sl0 = _c3_ref('halo_direct', 13, shape, dtype, 'plain')
+    dd = d[:, :, None, None].double()
     for det in (False, True):
         with sg2hip.deterministic(det, device=DEV):
             y, _, dot = cg.conv3x3_fused(xd, wp, Cout, out_scale=d.to(DEV),
                                          dot_src=src.to(DEV).contiguous(memory_format=torch.channels_last))
         assert rel_err(y.float(), c0 * d[:, :, None, None]) < tol
         assert rel_err(dot, (c0.to(dtype).double() * src.double()).sum([2, 3])) < tol
+        _elementwise(y, c0 * dd, EW.epilogue_slack(sl0, c0, dd), dtype, f'halo direct={direct} dgrad out_scale')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
@@ -687,6 +819,12 @@ def test_layer_bwd(dtype, shape):
     assert rel_err(db, dz.sum([0, 2, 3])) < 1e-4
     assert rel_err(dd, (dz * c.float()).sum([2, 3])) < 1e-4
     assert rel_err(dn, dz.sum(1, keepdim=True)) < 1e-4
+    # elementwise: dc = round(dy gain [alpha] d), no accumulation -- three f32 products before the one rounding; the
+    # masks come from the stored 16-bit y, so they are exact
+    yd = y.double().cpu()
+    ref = (dy.double().cpu() * 1.5 * torch.where(yd > 0, 1.0, float(np.float32(0.2))) * ((yd > -2.5) & (yd < 2.5)).double()
+           * d.double().cpu()[:, :, None, None])
+    _elementwise(dc, ref, 3 * EW.EPS32 * ref.abs(), dtype, 'layer_bwd dc')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
@@ -704,12 +842,47 @@ def test_conv3x3_dot_and_scaled_wgrad(dtype, shape):
     tol = 5e-3 if dtype == torch.float16 else 2e-2
     assert rel_err(y.float(), c * s[:, :, None, None].double()) < tol
     assert rel_err(dot, (c.to(dtype).double() * src.double()).sum([2, 3])) < tol
+    # elementwise on the out_scale output (no modulation: model 'plain'); the dot keeps the persistent c64p kernel on
+    # the second shape (the ring kernels have no dot epilogue), the first runs the register-staged halo kernel
+    cc, sl = _conv_ref(x.double().cpu(), w.double().cpu(), 9 * Cin, padding=1)
+    sd = s.double().cpu()[:, :, None, None]
+    _elementwise(y, cc * sd, EW.epilogue_slack(sl, cc, sd), dtype, f"dgrad out_scale {'c64p' if Cout == 64 else 'halo'}")
     g = torch.randn(N, Cout, H, W, device=DEV).to(dtype).contiguous(memory_format=torch.channels_last)
     xs = torch.rand(N, Cin, device=DEV) + 0.5
     dw = cg._wgrad_raw(g, x, 3, 3, 1, (1, 1), x_scale=xs)
     xsc = (x.float() * xs[:, :, None, None]).to(dtype)
     ref = torch.nn.grad.conv2d_weight(xsc.double(), w.shape, g.double(), padding=1)
     assert rel_err(dw, ref) < tol
+    if N * H * W <= 2220:
+        # elementwise where one dropped term still crosses the bound (N H W = 1320; the second shape sums 294 912 terms
+        # and stays on rel_err).  6 tiles a sample, 4 a workgroup: the register-staged kernel, round(x s) with s in f32
+        # ('x_f32s', the reference `xsc`)
+        _elementwise(dw, *EW.wgrad_ref(g.double().cpu(), xsc.double().cpu(), list(w.shape), padding=1), torch.float32,
+                     f'scaled wgrad {str(dtype)[6:]}[x_f32s]')
+
+
+@pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
+def test_conv3x3_c64p_modulated(dtype, monkeypatch):
+    """The persistent C = 64 kernel (conv3x3_c64p_kernel) with the modulation and the full epilogue, a form no other
+    test reaches since the ring kernel takes the shape first: with the ring off (SG2_C64_RING=0) the smallest shape its
+    gate accepts on 256 CUs (two 32 x 16 tiles per CU).  It modulates at its LDS store by the style rounded to the
+    activation type -- round(x round(s)), model 'x' -- and folds the gain into the epilogue terms (max(v, alpha v))."""
+    from torch_utils.ops import conv2d_gradfix as cg
+    monkeypatch.setenv('SG2_C64_RING', '0')
+    shape = (4, 64, 256, 256, 64)
+    N, C, H, W, _ = shape
+    assert N * (H // 16) * (W // 32) >= 2 * torch.cuda.get_device_properties(DEV).multi_processor_count
+    t = _c3_inputs('c64p', 5, shape)
+    y, raw = cg.conv3x3_fused(t['x'].to(DEV, dtype).contiguous(memory_format=torch.channels_last),
+                              cg._pack_conv(t['w'].to(DEV, dtype)), C, in_scale=t['s'].to(DEV), out_scale=t['d'].to(DEV),
+                              noise=t['noise'].to(DEV, dtype).reshape(N, H, W).contiguous(), noise_gain=0.3,
+                              bias=t['b'].to(DEV), act=1, alpha=0.2, gain=np.sqrt(2), clamp=1.5, want_raw=True)
+    cm, sl = _c3_ref('c64p', 5, shape, dtype, 'x')
+    ym, ysl = _c3_epilogue(t, cm, sl, dtype, demod=True, noise=True)
+    tol = 5e-3 if dtype == torch.float16 else 2e-2
+    assert rel_err(raw.float(), cm) < tol and rel_err(y.float(), ym) < tol
+    _elementwise(raw, cm, sl, dtype, 'c64p[x] raw')
+    _elementwise(y, ym, ysl, dtype, 'c64p[x] y')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
@@ -763,6 +936,22 @@ def test_wgrad3x3_halo(dtype, shape, scaled):
     xs = (x.float() * s[:, :, None, None]).to(dtype) if scaled else x
     ref = torch.nn.grad.conv2d_weight(xs.double(), [A, B, 3, 3], g.double(), padding=1)
     assert rel_err(dw, ref) < (2e-3 if dtype == torch.float16 else 1e-2)
+    # elementwise, f32 output (u = 0), K = N H W <= 2220 (test_elementwise_host.py: at these shapes one dropped
+    # (n, y, x) term crosses the bound).  Scaled, the model follows wgrad3x3_run's gate: the LDS-DMA kernel keeps
+    # x s in f32 -- it multiplies a workgroup's partial sums by the f32 s, which needs the workgroup's tiles inside
+    # one sample: tiles per workgroup a divisor >= 4 of the tiles per sample -- 'f32', here (2, 64, 64, 32, 32) and
+    # (1, 512, 512, 32, 32) with 4 tiles a sample; the others (6, 1, 6 tiles a sample) run the register-staged kernel,
+    # which writes round(x s), s in f32, to LDS -- 'x_f32s', the reference `xs` above.
+    gd = g.double().cpu()
+    if scaled and shape in ((2, 64, 64, 32, 32), (1, 512, 512, 32, 32)):
+        xm = EW.mod_x_f32(x.cpu(), s.cpu(), dtype)
+        rm, sl = EW.wgrad_ref(gd, xm, [A, B, 3, 3], f32_ops=3, padding=1)   # alpha * s, * u, * the partial sum
+        model = 'f32'
+    else:
+        xm = EW.mod_x_f32s(x.cpu(), s.cpu(), dtype) if scaled else x.double().cpu()
+        rm, sl = EW.wgrad_ref(gd, xm, [A, B, 3, 3], padding=1)
+        model = 'x_f32s' if scaled else 'plain'
+    _elementwise(dw, rm, sl, torch.float32, f'wgrad3x3 {str(dtype)[6:]}[{model}]')
 
 
 def _layer_grads(fwd, params, x0, dy, second_order):
@@ -993,6 +1182,7 @@ def test_wgrad_halo_phases(dtype, case, s2p, monkeypatch):
         ref, = torch.autograd.grad((y * g.to(dtype).double()).sum(), [w])
         dw = cg._wgrad_raw(g.to(dtype).contiguous(memory_format=torch.channels_last),
                            x.to(dtype).contiguous(memory_format=torch.channels_last), 3, 3, 2, (0, 0), x_scale=s)
+        ops, model = (g.to(dtype), xs, 2), 'x_f32s'
     elif case == 'conv_s2':
         x = torch.randn(N, Ci, 33, 41, device=DEV)
         w = torch.randn(Co, Ci, 3, 3, device=DEV, dtype=torch.float64, requires_grad=True)
@@ -1001,6 +1191,7 @@ def test_wgrad_halo_phases(dtype, case, s2p, monkeypatch):
         ref, = torch.autograd.grad((y * g.to(dtype).double()).sum(), [w])
         dw = cg._wgrad_raw(g.to(dtype).contiguous(memory_format=torch.channels_last),
                            x.to(dtype).contiguous(memory_format=torch.channels_last), 3, 3, 2, (0, 0))
+        ops, model = (g.to(dtype), x.to(dtype), 2), 'plain'
     elif case == 'convT_s2':
         x = torch.randn(N, Ci, 16, 20, device=DEV)
         s = torch.rand(N, Ci, device=DEV) + 0.5
@@ -1011,6 +1202,7 @@ def test_wgrad_halo_phases(dtype, case, s2p, monkeypatch):
         ref, = torch.autograd.grad((y * dt.to(dtype).double()).sum(), [wt])
         dw = cg._wgrad_raw(x.to(dtype).contiguous(memory_format=torch.channels_last),
                            dt.to(dtype).contiguous(memory_format=torch.channels_last), 3, 3, 2, (0, 0), g_scale=s)
+        ops, model = (xs, dt.to(dtype), 2), 'x_f32s'       # the scaled x is the sum's g operand, dt its x operand
     else:
         x = torch.randn(N, Ci, 24, 20, device=DEV)
         w = torch.randn(Co, Ci, 1, 1, device=DEV, dtype=torch.float64, requires_grad=True)
@@ -1019,7 +1211,14 @@ def test_wgrad_halo_phases(dtype, case, s2p, monkeypatch):
         ref, = torch.autograd.grad((y * g.to(dtype).double()).sum(), [w])
         dw = cg._wgrad_raw(g.to(dtype).contiguous(memory_format=torch.channels_last),
                            x.to(dtype).contiguous(memory_format=torch.channels_last), 1, 1, 1, (0, 0))
+        ops, model = (g.to(dtype), x.to(dtype), 1), 'plain'
     assert rel_err(dw, ref) < (2e-3 if dtype == torch.float16 else 1e-2)
+    # elementwise, f32 output, K = N OH OW = 640 .. 3168 (test_elementwise_host.py: one dropped term crosses the bound
+    # at each of these; conv_s2_wide above, 18 432 terms, is too large for that and stays on rel_err).  The scaled cases
+    # run register-staged kernels (the LDS-DMA weight gradient is stride 1 only), which write round(x s), s in f32, to
+    # LDS: 'x_f32s', what `xs` replays.
+    rm, sl = EW.wgrad_ref(ops[0].double().cpu(), ops[1].double().cpu(), list(ref.shape), stride=ops[2])
+    _elementwise(dw, rm, sl, torch.float32, f'wgrad phases {case} s2p={s2p} {str(dtype)[6:]}[{model}]')
 
 
 @pytest.mark.parametrize('dp', [0.02, 0.5, 0.97])
@@ -1104,6 +1303,18 @@ def test_conv1x1_small_depth(dtype, cin, cout):
         z = (torch.where(z > 0, z, z * 0.2) * 1.4).clamp(-2.5, 2.5)
         assert rel_err(aux.float(), c if aux_mode == 1 else z) < tol, (cin, cout, aux_mode)
         assert rel_err(y.float(), z.to(dtype).double() + res.double()) < tol, (cin, cout, aux_mode)
+        # elementwise.  Rounding model of conv.hip's kernels: round(x s) with s left in f32 -- the f32 product
+        # `v * in_scale` rounded to T, which `xs` above replays operation for operation (callers that want the
+        # reference's x * s.to(x.dtype) pass a rounded s); bias and noise are 16-bit here; K = cin
+        f32 = lambda v: float(np.float32(v))
+        sl = EW.accumulation_slack(cin, F.conv2d(xs.abs(), wt.double().abs()))
+        so, ng, bb = s_out[:, :, None, None].double(), noise[:, None].double() * f32(0.3), bias[None, :, None, None].double()
+        zm = c * so + ng + bb
+        zm = (torch.where(zm > 0, zm, zm * f32(0.2)) * f32(1.4)).clamp(-2.5, 2.5)
+        zsl = EW.epilogue_slack(sl, c, so, ng, bb, f32(1.4), f32(0.2))
+        what = f'conv1x1 {cin}->{cout} aux_mode {aux_mode}'
+        _elementwise(aux, *((c, sl) if aux_mode == 1 else (zm, zsl)), dtype, what + ' aux')
+        _elementwise(y, *EW.add_residual(zm, zsl, res, dtype), dtype, what + ' y')
     # weight gradient of the 1x1 conv with both operands modulated
     g = torch.randn(n, cout, h, w).to(dtype)
     gs, xsc = torch.rand(n, cout) + 0.5, torch.rand(n, cin) + 0.5
@@ -1266,6 +1477,10 @@ def test_conv3x3_up2(dtype, shape, mod, monkeypatch):
     assert y.shape == ref.shape
     tol = 5e-3 if dtype == torch.float16 else 2e-2
     assert rel_err(y.float(), ref) < tol
+    # elementwise: the up-2 kernel modulates round(x round(s)) in its staging (model 'x', the reference above); an
+    # output pixel sums the taps of its phase, at most 4 of the 9, so K = 4 Cin
+    rc, sl = _conv_ref(xs.double().cpu(), w.double().transpose(0, 1).cpu(), 4 * Cin, conv=F.conv_transpose2d, stride=2)
+    _elementwise(y, rc, sl, dtype, f"up2[{'x' if mod else 'plain'}]")
     if H % 8 == 0 and W % 16 == 0:   # the edge split (last cell row / column as three-tap strips): the same sums
         monkeypatch.setenv('SG2_UP2_EDGE', '0')
         ys = cg._conv_up2(x, cg._pack_conv(w), Cout, in_scale=s)
@@ -1306,6 +1521,15 @@ def test_conv3x3_s2(dtype, shape):
     assert y.shape == (N, Cout, OH, OW)
     assert rel_err(raw.float(), c) < tol
     assert rel_err(y.float(), yr) < tol
+    # elementwise.  Forms (1) and (3) run the 32 x 4 stride-2 halo kernel (modulation, noise or dot keep the s2g
+    # kernel out), which modulates round(x round(s)) at its LDS write: model 'x'.  Form (2) has no modulation and
+    # takes the s2g kernel where its gate accepts the shape; both kernels round the bias to the activation type and
+    # add the residual as round(round(v) + residual), so one model serves it.
+    t = dict(d=d, noise=noise, b=b)
+    wd = w.to(dtype).double()
+    cx, slx = _conv_ref(EW.mod_x(x, s, dtype), wd, 9 * Cin, stride=2)
+    _elementwise(raw, cx, slx, dtype, 's2 halo[x] raw')
+    _elementwise(y, *_c3_epilogue(t, cx, slx, dtype, demod=True, noise=True), dtype, 's2 halo[x] y')
     # (2) bias + lrelu + residual (DiscriminatorBlock conv1), raw = the activation before the add
     rd = res.to(DEV, dtype).contiguous(memory_format=torch.channels_last)
     y, za = cg.conv3x3_fused(xd, wp, Cout, bias=b.to(DEV), act=1, alpha=0.2, gain=np.sqrt(0.5), clamp=256.0,
@@ -1315,6 +1539,10 @@ def test_conv3x3_s2(dtype, shape):
     assert rel_err(za.float(), zr) < tol
     assert rel_err(y.float(), zr + res.to(dtype).double()) < tol
     assert torch.equal(y, (za.float() + rd.float()).to(dtype))     # round(z) + residual, rounded once more
+    _, sl0 = _conv_ref(x.to(dtype).double(), wd, 9 * Cin, stride=2)
+    zm, zsl = _c3_epilogue(t, c0, sl0, dtype, gain=np.sqrt(0.5), clamp=256.0)
+    _elementwise(za, zm, zsl, dtype, 's2 raw_act')
+    _elementwise(y, *EW.add_residual(zm, zsl, res, dtype), dtype, 's2 residual y')
     # (3) out_scale + dot (the up-2 layer's dgrad: dx and ds in one launch)
     src = torch.randn(N, Cout, OH, OW).to(dtype)
     y, _, dot = cg.conv3x3_fused(xd, wp, Cout, out_scale=d.to(DEV), dot_src=src.to(DEV).contiguous(
@@ -1322,6 +1550,8 @@ def test_conv3x3_s2(dtype, shape):
     cd = F.conv2d(x.to(dtype).double(), w.to(dtype).double(), stride=2)
     assert rel_err(y.float(), cd * d[:, :, None, None]) < tol
     assert rel_err(dot, (cd * src.double()).sum([2, 3])) < tol
+    dd = d[:, :, None, None].double()
+    _elementwise(y, cd * dd, EW.epilogue_slack(sl0, cd, dd), dtype, 's2 halo out_scale')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
@@ -1353,19 +1583,37 @@ def test_conv3x3_s2g(dtype, shape, s2g, monkeypatch):
     assert y.shape == (N, Cout, OH, OW) and rel_err(y.float(), c) < tol
     for n in range(N):
         assert rel_err(y[n].float(), c[n]) < tol, n
+    # elementwise: neither route modulates here (the s2g gate refuses in_scale), so the model is 'plain' with the bias
+    # rounded to the activation type and the residual added as round(round(v) + residual) -- the same points in the
+    # s2g kernel (s2g '1') and the 32 x 4 halo kernel (s2g '0')
+    t = dict(d=d, b=b)
+    _, sl = _conv_ref(x.to(dtype).double(), w.to(dtype).double(), 9 * Cin, stride=2)
+
+    def ew(got, ref, slack, what):
+        _elementwise(got, ref, slack, dtype, f's2g={s2g} {what}')
+
+    ew(y, c, sl, 'plain')
     y, raw = cg.conv3x3_fused(xd, wp, Cout, bias=b.to(DEV), act=1, alpha=0.2, gain=np.sqrt(2), clamp=1.5,
                               want_raw=True, stride=2)
     assert rel_err(raw.float(), c) < tol
     assert rel_err(y.float(), (F.leaky_relu(c + b[None, :, None, None], 0.2) * np.sqrt(2)).clamp(-1.5, 1.5)) < tol
+    ew(raw, c, sl, 'dblock raw')
+    ew(y, *_c3_epilogue(t, c, sl, dtype), 'dblock y')
     rd = res.to(DEV, dtype).contiguous(memory_format=torch.channels_last)
     y, za = cg.conv3x3_fused(xd, wp, Cout, bias=b.to(DEV), act=1, alpha=0.2, gain=np.sqrt(0.5), clamp=256.0,
                              want_raw=True, stride=2, residual=rd, raw_act=True)
     zr = F.leaky_relu(c + b[None, :, None, None], 0.2) * np.sqrt(0.5)
     assert rel_err(za.float(), zr) < tol
     assert torch.equal(y, (za.float() + rd.float()).to(dtype))            # round(z) + residual, rounded once more
+    zm, zsl = _c3_epilogue(t, c, sl, dtype, gain=np.sqrt(0.5), clamp=256.0)
+    ew(za, zm, zsl, 'raw_act')
+    ew(y, *EW.add_residual(zm, zsl, res, dtype), 'residual y')
     y, raw = cg.conv3x3_fused(xd, wp, Cout, out_scale=d.to(DEV), want_raw=True, stride=2, residual=rd)
     assert rel_err(raw.float(), c) < tol
     assert rel_err(y.float(), c * d[:, :, None, None] + res.to(dtype).double()) < tol
+    dd = d[:, :, None, None].double()
+    ew(raw, c, sl, 'out_scale raw')
+    ew(y, *EW.add_residual(c * dd, EW.epilogue_slack(sl, c, dd), res, dtype), 'out_scale + residual y')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])
@@ -1557,13 +1805,8 @@ def test_conv3x3_c64_ring(dtype, shape, form, ring, monkeypatch):
     th = 4 if ring in ('4', '44', '46', '49') else 8
     wgs = (2 if th == 4 else 1) * torch.cuda.get_device_properties(DEV).multi_processor_count
     assert N * (H // th) * (W // 32) >= 2 * wgs      # the ring kernel's minimum of two tiles per workgroup
-    torch.manual_seed(17)
-    x = torch.randn(N, C, H, W)
-    w = torch.randn(C, C, 3, 3) / np.sqrt(C * 9)
-    s = torch.rand(N, C) + 0.5
-    d = torch.rand(N, C) + 0.5
-    noise = torch.randn(N, 1, H, W)
-    b = torch.randn(C) * 0.1
+    t = _c3_inputs('c64_ring', 17, (N, C, H, W, C))
+    x, w, s, d, noise, b = (t[k] for k in ('x', 'w', 's', 'd', 'noise', 'b'))
     mod = form.startswith('mod')
     epi = 'epi' in form
     demod_noise = form.startswith('mod_epi')
@@ -1577,8 +1820,7 @@ def test_conv3x3_c64_ring(dtype, shape, form, ring, monkeypatch):
     xd = x.to(DEV, dtype).contiguous(memory_format=torch.channels_last)
     wp = cg._pack_conv(w.to(DEV, dtype))
     y, raw = cg.conv3x3_fused(xd, wp, C, in_scale=s.to(DEV) if mod else None, want_raw=form.endswith('raw'), **kw)
-    xs = (x.to(dtype).float() * s[:, :, None, None]).to(dtype).double() if mod else x.to(dtype).double()
-    c = F.conv2d(xs, w.to(dtype).double(), padding=1)
+    c, _ = _c3_ref('c64_ring', 17, (N, C, H, W, C), dtype, 'legacy' if mod else 'plain')
     ref = c
     if epi:
         z = c * (d[:, :, None, None] if (demod_noise or form == 'epi_no_noise') else 1)
@@ -1596,6 +1838,14 @@ def test_conv3x3_c64_ring(dtype, shape, form, ring, monkeypatch):
     edge = torch.zeros(H, W, dtype=torch.bool)
     edge[0], edge[-1], edge[:, 0], edge[:, -1] = True, True, True, True
     assert rel_err(y.float()[..., edge], ref[..., edge]) < 2 * tol
+    # elementwise: every ring form modulates on the weight side, round(W round(s)) per sample (model 'w')
+    model = 'w' if mod else 'plain'
+    cm, sl = _c3_ref('c64_ring', 17, (N, C, H, W, C), dtype, model)
+    em, esl = (_c3_epilogue(t, cm, sl, dtype, demod=demod_noise or form == 'epi_no_noise', noise=demod_noise)
+               if epi else (cm, sl))
+    _elementwise(y, em, esl, dtype, f'c64 ring {ring} {form}[{model}] y')
+    if form.endswith('raw'):
+        _elementwise(raw, cm, sl, dtype, f'c64 ring {ring} {form}[{model}] raw')
 
 
 @pytest.mark.parametrize('form', ['mod_epi_raw', 'plain'])
@@ -1620,13 +1870,8 @@ def test_conv3x3_c32_ring(dtype, shape, form, ring32, monkeypatch):
     C = 32
     wgs = 2 * torch.cuda.get_device_properties(DEV).multi_processor_count
     assert N * (H // 8) * (W // 32) >= 2 * wgs      # the ring kernel's minimum of two tiles per workgroup
-    torch.manual_seed(19)
-    x = torch.randn(N, C, H, W)
-    w = torch.randn(C, C, 3, 3) / np.sqrt(C * 9)
-    s = torch.rand(N, C) + 0.5
-    d = torch.rand(N, C) + 0.5
-    noise = torch.randn(N, 1, H, W)
-    b = torch.randn(C) * 0.1
+    t = _c3_inputs('c32_ring', 19, (N, C, H, W, C))
+    x, w, s, d, noise, b = (t[k] for k in ('x', 'w', 's', 'd', 'noise', 'b'))
     mod = form.startswith('mod')
     epi = 'epi' in form
     demod_noise = form.startswith('mod_epi')
@@ -1640,8 +1885,7 @@ def test_conv3x3_c32_ring(dtype, shape, form, ring32, monkeypatch):
     xd = x.to(DEV, dtype).contiguous(memory_format=torch.channels_last)
     wp = cg._pack_conv(w.to(DEV, dtype))
     y, raw = cg.conv3x3_fused(xd, wp, C, in_scale=s.to(DEV) if mod else None, want_raw=form.endswith('raw'), **kw)
-    xs = (x.to(dtype).float() * s[:, :, None, None]).to(dtype).double() if mod else x.to(dtype).double()
-    c = F.conv2d(xs, w.to(dtype).double(), padding=1)
+    c, _ = _c3_ref('c32_ring', 19, (N, C, H, W, C), dtype, 'legacy' if mod else 'plain')
     ref = c
     if epi:
         z = c * (d[:, :, None, None] if (demod_noise or form == 'epi_no_noise') else 1)
@@ -1658,6 +1902,15 @@ def test_conv3x3_c32_ring(dtype, shape, form, ring32, monkeypatch):
     edge = torch.zeros(H, W, dtype=torch.bool)
     edge[0], edge[-1], edge[:, 0], edge[:, -1] = True, True, True, True
     assert rel_err(y.float()[..., edge], ref[..., edge]) < 2 * tol
+    # elementwise: the ring modulates on the weight side (model 'w'); with ring32 '0' the shape falls to the
+    # register-staged halo kernel (Cout % 64 != 0 keeps the LDS-DMA form out), which rounds round(x round(s)) ('x')
+    model = ('w' if ring32 == '1' else 'x') if mod else 'plain'
+    cm, sl = _c3_ref('c32_ring', 19, (N, C, H, W, C), dtype, model)
+    em, esl = (_c3_epilogue(t, cm, sl, dtype, demod=demod_noise or form == 'epi_no_noise', noise=demod_noise)
+               if epi else (cm, sl))
+    _elementwise(y, em, esl, dtype, f'c32 ring32={ring32} {form}[{model}] y')
+    if form.endswith('raw'):
+        _elementwise(raw, cm, sl, dtype, f'c32 ring32={ring32} {form}[{model}] raw')
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16, torch.float32])
