@@ -83,9 +83,25 @@ __global__ __launch_bounds__(256) void det_sum_vec4_kernel(float* out, int64_t g
     *o = r;
 }
 
+// The vec4 form's arithmetic one output a lane, for the shapes the vec4 form takes when `out` or `ws` is not 16-byte
+// aligned (a slice of a caller's accumulator at an odd offset): s = 0, 1, ..., S - 1 in order, then the one add into
+// out -- bit for bit what det_sum_vec4_kernel gives, so the result does not depend on where the output sits.
+__global__ __launch_bounds__(256) void det_sum_seq_kernel(float* out, int64_t go, const float* ws, int64_t gw,
+                                                          int64_t ss, int64_t S, int64_t n, int assign) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t g = blockIdx.y;
+    if (i >= n) return;
+    const float* w = ws + g * gw + i;
+    float acc = w[0];
+    for (int64_t s = 1; s < S; ++s) acc += w[s * ss];
+    float* o = out + g * go + i;
+    *o = assign ? acc : *o + acc;
+}
+
 // Several independent sums in one launch (the pairs of sums one kernel's slots feed, e.g. sg2_layer_bwd's bias and
 // demodulation gradients): workgroup b belongs to the job whose block range holds it and runs det_sum_kernel's body
-// for that job's (i block, g, chunk).
+// for that job's (i block, g, chunk).  Always the four-row order: this launch never takes the sequential (vec4)
+// form that det_sum picks at S <= kVecS over many outputs.
 struct DetJob {
     float* out;
     const float* ws;
@@ -178,11 +194,16 @@ hipError_t det_sum(float* out, int64_t go, const float* ws, int64_t gw, int64_t 
     static const bool trace = getenv("SG2_DET_TRACE") != nullptr;   // diagnostics: one line per call (tools/)
     const int64_t S0 = S;
     const int64_t bx = cdiv(n, kLanes);
-    if (S <= kVecS && n % 4 == 0 && go % 4 == 0 && gw % 4 == 0 && ss % 4 == 0 && (uintptr_t)out % 16 == 0 &&
-        (uintptr_t)ws % 16 == 0 && bx * G >= 512) {
+    // the order (s in sequence, or four interleaved rows) is chosen from the shapes and strides alone; the pointers'
+    // alignment only picks the kernel that carries out the sequential order
+    if (S <= kVecS && n % 4 == 0 && go % 4 == 0 && gw % 4 == 0 && ss % 4 == 0 && bx * G >= 512) {
         if (trace) fprintf(stderr, "DETSUM G=%d n=%lld S=%lld K=%lld\n", G, (long long)n, (long long)S, 1LL);
-        det_sum_vec4_kernel<<<dim3((unsigned)cdiv(n / 4, 256), (unsigned)G, 1), 256, 0, st>>>(out, go, ws, gw, ss, S,
-                                                                                             n / 4, assign);
+        if ((uintptr_t)out % 16 == 0 && (uintptr_t)ws % 16 == 0)
+            det_sum_vec4_kernel<<<dim3((unsigned)cdiv(n / 4, 256), (unsigned)G, 1), 256, 0, st>>>(out, go, ws, gw, ss,
+                                                                                                 S, n / 4, assign);
+        else
+            det_sum_seq_kernel<<<dim3((unsigned)cdiv(n, 256), (unsigned)G, 1), 256, 0, st>>>(out, go, ws, gw, ss, S, n,
+                                                                                            assign);
         return hipGetLastError();
     }
     // few outputs over a long sum (a bias or dot reduction over every pixel block): first chunks of the s range in

@@ -31,6 +31,7 @@ struct LBArgs {
     int act;             // 0 linear, 1 lrelu
     float* det_db;       // deterministic mode: [gridDim.y * gridDim.x][C] slot partials of db
     float* det_dd;       // deterministic mode: [gridDim.x][N * C] slot partials of dd
+    int dn_part;         // deterministic mode, C / 8 no power of two: LDS offset of [pix_per_block][C / 8] dnoise partials
 };
 
 template <typename T>
@@ -64,7 +65,8 @@ __global__ __launch_bounds__(256) void layer_bwd_kernel(LBArgs a) {
     T* dcp = (T*)a.dc;
     // U pixels per lane per iteration, all loads issued first (raw buffer loads: a pixel past the block
     // reads zeros); the noise gradient sums the LP lanes of a pixel with xor shuffles when LP is a power
-    // of two <= 64 (C <= 512), else through LDS atomics.
+    // of two <= 64 (C <= 512), else through LDS atomics -- in deterministic mode through one LDS partial per lane
+    // (dn_part), added in lane order at the end: the atomics' order varies from run to run.
     constexpr int U = 4;
     constexpr int V = 16 / sizeof(T) < 8 ? 16 / sizeof(T) : 8;   // elements per 16-byte load
     constexpr int NL = 8 / V;                                     // 16-byte loads per 8 channels
@@ -116,7 +118,8 @@ __global__ __launch_bounds__(256) void layer_bwd_kernel(LBArgs a) {
                         for (int m = 1; m < LP; m <<= 1) psum += __shfl_xor(psum, m);
                         if (cg == 0 && p < p1) a.dnoise[(int64_t)n * a.HW + p] = psum;
                     } else if (p < p1) {
-                        atomicAdd(&s_dn[p - p0], psum);
+                        if (a.dn_part) sm[a.dn_part + (p - p0) * LP + cg] = psum;
+                        else atomicAdd(&s_dn[p - p0], psum);
                     }
                 }
             }
@@ -154,7 +157,14 @@ __global__ __launch_bounds__(256) void layer_bwd_kernel(LBArgs a) {
         }
     }
     if (a.dnoise && !shfl)
-        for (int p = p0 + tid; p < p1; p += 256) a.dnoise[(int64_t)n * a.HW + p] = s_dn[p - p0];
+        for (int p = p0 + tid; p < p1; p += 256) {
+            float v = s_dn[p - p0];
+            if (a.dn_part) {
+                v = 0.f;
+                for (int q = 0; q < LP; ++q) v += sm[a.dn_part + (p - p0) * LP + q];
+            }
+            a.dnoise[(int64_t)n * a.HW + p] = v;
+        }
 }
 
 // out[n, c] = sum_p a[n, p, c] * b[n, p, c] over the pixels of NHWC tensors, f32 accumulation: the
@@ -371,7 +381,11 @@ extern "C" int sg2_layer_bwd(void* dc, float* db, float* dd, float* dnoise, cons
     if (det_on() && dnoise) SG2_CHECK(LP <= 64, "sg2_layer_bwd: deterministic mode needs C <= 512 with dnoise");
     if (det && db) SG2_DET_GET(a.det_db, arena, (int64_t)grid.x * N * C, "sg2_layer_bwd");
     if (det && dd) SG2_DET_GET(a.det_dd, arena, (int64_t)grid.x * N * C, "sg2_layer_bwd");
-    const size_t lds = (2 * C + a.pix_per_block + (det ? PPP * C : 0)) * sizeof(float);
+    size_t lds = (2 * C + a.pix_per_block + (det ? PPP * C : 0)) * sizeof(float);
+    if (det_on() && dnoise && (LP & (LP - 1)) != 0) {   // the kernel's !shfl form (LP <= 64 here): ordered noise sums
+        a.dn_part = (int)(lds / sizeof(float));
+        lds += (size_t)a.pix_per_block * LP * sizeof(float);   // <= 16 PPP LP <= 4096 floats
+    }
     if (dtype == SG2_F16) layer_bwd_kernel<f16_t><<<grid, 256, lds, s>>>(a);
     else if (dtype == SG2_BF16) layer_bwd_kernel<bf16_t><<<grid, 256, lds, s>>>(a);
     else layer_bwd_kernel<float><<<grid, 256, lds, s>>>(a);

@@ -68,13 +68,16 @@ class DetArena {
     int64_t cap_, off_;
 };
 // out[g * go + i] += sum_{s < S} ws[g * gw + s * ss + i] for g < G (<= 65535), i < n: a fixed-order sum (four
-// interleaved row sums over s, s = r mod 4 in increasing s, added in row order; at S <= 16 over many outputs, s in
-// increasing order four outputs a lane; det.hip), one launch, or two (a chunk pass into `arena`) for few outputs
-// over many slots.
+// interleaved row sums over s, s = r mod 4 in increasing s, added in row order; at S <= 16 over many outputs with
+// n, go, gw, ss all multiples of 4, s in increasing order; det.hip), one launch, or two (a chunk pass into `arena`)
+// for few outputs over many slots.  The order follows from the shapes and strides alone, never from the addresses
+// of out or ws.
 hipError_t det_sum(float* out, int64_t go, const float* ws, int64_t gw, int64_t ss, int G, int64_t S, int64_t n,
                    DetArena& arena, hipStream_t st, int assign = 0);   // assign: out = instead of out +=
 // Up to four independent det_sum calls in (at most) two launches: the chunk passes of those that need one
-// together, then the final sums together; each job's order is det_sum's.
+// together, then the final sums together.  Each job is summed in det_sum's four-row order (with its chunk pass),
+// also at the shapes where det_sum itself would add s in sequence (S <= 16 over many outputs): a job's bits equal
+// det_sum's for the same shapes only outside those, and always equal det_sum_multi's own from run to run.
 struct DetSumJob {
     float* out;
     int64_t go;

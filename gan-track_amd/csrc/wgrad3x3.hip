@@ -761,6 +761,13 @@ int w3_det_slots(W3Args& a, DetArena& arena, int slots, hipStream_t s, bool zero
     return 0;
 }
 
+// Every workgroup split (blockIdx.z) owns at least one tile: the kernels return early on an empty tile range, and
+// in deterministic mode a slot that no workgroup writes would put stale scratch into dw (the slot arrays of the
+// single-phase launches are not zeroed, and det_sum assigns).  Checked after any adjustment of tiles_per_block.
+inline bool w3_grid_covers(const W3Args& a, const dim3& grid) {
+    return grid.z >= 1 && a.tiles_per_block >= 1 && (int64_t)(grid.z - 1) * a.tiles_per_block < a.tiles;
+}
+
 int wgrad3x3_run(W3Args& a, DetArena& arena, float* dw, const void* g, const void* x, const float* gscale,
                  const float* xscale, int dtype, int N, int A, int OH, int OW, int B, int H, int W, int KH, int KW,
                  int stride, int pad_y, int pad_x, float alpha, hipStream_t s) {
@@ -781,6 +788,7 @@ int wgrad3x3_run(W3Args& a, DetArena& arena, float* dw, const void* g, const voi
         a.tiles_per_block = (int)cdiv(a.tiles, splits);
         splits = (int)cdiv(a.tiles, a.tiles_per_block);
         dim3 grid((unsigned)cdiv(A, BC), (unsigned)cdiv(B, BC), (unsigned)splits);
+        SG2_CHECK(w3_grid_covers(a, grid), "sg2_conv2d_wgrad (halo): a workgroup split without tiles");
         if (int rc = w3_det_slots(a, arena, (int)grid.z, s)) return rc;
         static const bool swz = [] { const char* e = getenv("SG2_WGRAD_SWZ"); return e != nullptr && e[0] == '1'; }();
         if (pipe) {
@@ -826,6 +834,7 @@ int wgrad3x3_run(W3Args& a, DetArena& arena, float* dw, const void* g, const voi
             for (int kx = 0; kx < KW; ++kx)
                 a.taps[ky * KW + kx] = PTap{(int8_t)(ky - pad_y), (int8_t)(kx - pad_x), (int8_t)(ky * KW + kx), 0};
         a.PY = 0; a.PX = 0;
+        SG2_CHECK(w3_grid_covers(a, grid), "sg2_conv2d_wgrad (halo): a workgroup split without tiles");
         if (int rc = w3_det_slots(a, arena, (int)grid.z, s)) return rc;
         const int sel = ((gscale || xscale) ? 1 : 0) | (KH == 3 ? 2 : 0) | (TW == 32 ? 4 : 0) | (dtype == SG2_F16 ? 8 : 0);
         switch (sel) {
@@ -844,6 +853,7 @@ int wgrad3x3_run(W3Args& a, DetArena& arena, float* dw, const void* g, const voi
         }
         return launch_status("sg2_conv2d_wgrad (halo, LDS-DMA)");
     }
+    SG2_CHECK(w3_grid_covers(a, grid), "sg2_conv2d_wgrad (halo): a workgroup split without tiles");
     if (int rc = w3_det_slots(a, arena, (int)grid.z, s, stride > 1)) return rc;
     for (int py = 0; py < stride; ++py)
         for (int px = 0; px < stride; ++px) {

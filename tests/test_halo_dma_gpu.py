@@ -13,10 +13,17 @@ import torch
 import torch.nn.functional as F
 
 import elementwise as EW
+import poison
 from golden_util import rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device('cuda', 0)
+
+
+@pytest.fixture(autouse=True)
+def _poisoned_empties(request, monkeypatch):
+    """Every torch.empty / empty_like of the op wrappers comes back NaN-filled (tests/poison.py)."""
+    poison.poisoned_empties(monkeypatch, poison.op_modules(request.node.originalname))
 
 # (N, Cin, H, W, Cout): the smallest shapes at which each part of the staging can go wrong
 SHAPES = [
