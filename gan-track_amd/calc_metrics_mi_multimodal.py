@@ -3,7 +3,7 @@ on the G_ema of a network pickle, one JSON line per evaluation printed and (insi
 appended to metric-<modality>-<metric>.jsonl.
 
     python calc_metrics_mi_multimodal.py --network <run_dir>/network-snapshot-000200.pkl \\
-        --metrics fid50k_full,pr50k3_full,ppl2_wend
+        --metrics fid50k_full,kid50k,pr50k3_full,ppl2_wend
 
 The dataset options come from --data, or else from the snapshot's own training_set_kwargs.  The snapshot is read by
 this build's legacy.load_network_pkl (nothing embedded in the pickle is executed) and must be a local file; the
@@ -135,6 +135,7 @@ def calc_metrics(**kwargs):
       ppl2_wend    Perceptual path length in W, endpoints, full image.
       fid50k       Frechet inception distance against 50k real images.
       pr50k3       Precision and recall against 50k real images.
+      kid50k       Kernel inception distance against 50k real images.
     """
     args = build_args(**kwargs)
     if args.verbose:

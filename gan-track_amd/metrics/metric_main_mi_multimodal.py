@@ -3,7 +3,8 @@ keeps the reference's entry points (register_metric, is_valid_metric, list_valid
 report_metric) and its output contract (one JSON line per evaluation appended to
 <run_dir>/metric-<modality>-<metric>.jsonl); the FID metrics are the two the Claro / Pelvis runs name, the
 precision / recall metrics (pr50k3_full, pr50k3) the one further metric the reference adapted to its per-modality
-evaluation, and ppl2_wend the perceptual path length its offline evaluation (calc_metrics_mi_multimodal.py) names."""
+evaluation, and ppl2_wend the perceptual path length and kid50k the kernel inception distance its offline
+evaluation (calc_metrics_mi_multimodal.py) names."""
 import json
 import os
 import time
@@ -15,6 +16,7 @@ from . import metric_utils
 from . import frechet_inception_distance
 from . import precision_recall
 from . import perceptual_path_length
+from . import kernel_inception_distance
 
 
 class _Registry:
@@ -126,3 +128,14 @@ def ppl2_wend(opts):
     ppl = perceptual_path_length.compute_ppl(opts, num_samples=50000, epsilon=1e-4, space='w', sampling='end',
                                              crop=False, batch_size=2)
     return dict(ppl2_wend=ppl)
+
+
+@register_metric
+def kid50k(opts):
+    """Kernel inception distance, 100 subsets of up to 1000, against 50k real images (:141-144).  (kid50k_full --
+    the same with xflip off and the cap on the real set lifted to 10^6 -- draws from the same real set on every
+    dataset below 50 000 images and is not registered.)"""
+    opts.dataset_kwargs.update(max_size=None)
+    kid = kernel_inception_distance.compute_kid(opts, max_real=50000, num_gen=50000, num_subsets=100,
+                                                max_subset_size=1000)
+    return dict(kid50k=kid)

@@ -96,6 +96,9 @@ SIGNATURES = {
     'sg2_ppl_prep': [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     'sg2_lpips_pair_dist_scratch_bytes': [_c_i64p, _i64, _i64],
     'sg2_lpips_pair_dist': [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _i64, _vp],
+    # (additive to ABI 11: the kernel inception distance's MMD sums, csrc/mmd.hip)
+    'sg2_poly_mmd_scratch_bytes': [_c_i64p, _i, _i],
+    'sg2_poly_mmd_sums': [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _i64, _vp],
 }
 ABI_VERSION = 11
 

@@ -463,6 +463,26 @@ int sg2_lpips_pair_dist_scratch_bytes(int64_t* bytes, int64_t B, int64_t F);
 int sg2_lpips_pair_dist(float* dist, const float* feats, int64_t B, int64_t F, double eps, void* scratch,
                         int64_t scratch_bytes, void* stream);
 
+/* The polynomial-kernel MMD sums of the kernel inception distance (SG3/metrics/kernel_inception_distance.py:33-44).
+ * ADDITIVE entry points: SG2_ABI_VERSION stays 11.
+ *
+ * gen f32 [n_gen, d] and real f32 [n_real, d] row-major, 16-byte aligned, any size (row addresses are 64-bit);
+ * idx_gen, idx_real: DEVICE int32 [S, m] tables of row numbers, TRUSTED (0 <= idx < n is the caller's to check).
+ * With x_i = gen[idx_gen[s][i]], y_j = real[idx_real[s][j]] and k(a, b) = (a.b / d + 1)^3,
+ *   sums[s] = ( sum_{i != j} k(x_i, x_j),  sum_{i != j} k(y_i, y_j),  sum_{i, j} k(x_i, y_j) )     (f64 [S, 3], device)
+ * where i != j compares subset POSITIONS, not row numbers: a row drawn twice counts as two points.
+ * The dot product is an exact-f32 fma chain (the f32-input MFMA); / d, + 1 and the cube are f32 operations, as in
+ * float32 numpy; every addition of kernel values is f64 in an order fixed by (S, m) alone, without atomics: two calls
+ * give the same bits.  Neither a gathered [S, m, d] copy nor an m x m matrix is written to memory.
+ * d >= 4 and d % 4 == 0, m >= 2, S >= 1, n_gen and n_real >= 1; anything else is an argument error and nothing is
+ * launched.  2 launches.
+ * sg2_poly_mmd_scratch_bytes: the scratch (one f64 per 128 x 128 tile) the call needs; a shorter one is an argument
+ *   error.  Every scratch element the call reads it has written itself. */
+int sg2_poly_mmd_scratch_bytes(int64_t* bytes, int S, int m);
+int sg2_poly_mmd_sums(double* sums, const float* gen, int64_t n_gen, const float* real, int64_t n_real,
+                      const int32_t* idx_gen, const int32_t* idx_real, int S, int m, int d, void* scratch,
+                      int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
