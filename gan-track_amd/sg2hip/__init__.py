@@ -99,6 +99,8 @@ SIGNATURES = {
     # (additive to ABI 11: the kernel inception distance's MMD sums, csrc/mmd.hip)
     'sg2_poly_mmd_scratch_bytes': [_c_i64p, _i, _i],
     'sg2_poly_mmd_sums': [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _i64, _vp],
+    # (additive to ABI 11: the generator's output stage, images -> uint8 canvas tiles, csrc/imgout.hip)
+    'sg2_image_tiles_u8': [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _i, _i, _i64, _vp],
 }
 ABI_VERSION = 11
 

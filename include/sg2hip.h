@@ -483,6 +483,33 @@ int sg2_poly_mmd_sums(double* sums, const float* gen, int64_t n_gen, const float
                       const int32_t* idx_gen, const int32_t* idx_real, int S, int m, int d, void* scratch,
                       int64_t scratch_bytes, void* stream);
 
+/* The generator's output stage: images -> uint8 tiles of an HWC canvas in one launch (SG3/gen_video.py layout_grid,
+ * gen_images*.py, save_image / save_image_grid; csrc/imgout.hip).  ADDITIVE entry point: SG2_ABI_VERSION stays 11.
+ *
+ * img [N, C, H, W] contiguous, dtype SG2_F32 / SG2_F16 / SG2_BF16 (16-bit values are widened to f32 first, exactly);
+ * canvas uint8 [gh * H, gw * W, Cout] contiguous (HWC: what an image or video writer takes), any byte alignment.
+ * tiles:  a channel k >= 0     tile n = channel k of image n,           Cout = 1, T = N tiles
+ *         SG2_TILES_GREY       tile n * C + c = channel c of image n,   Cout = 1, T = N * C
+ *         SG2_TILES_HWC        tile n = image n, channels interleaved,  Cout = C in {1, 3}, T = N
+ * Tile t goes to grid cell first_tile + t: row (first_tile + t) / gw, column (first_tile + t) % gw;
+ * first_tile + T > gw * gh is an argument error.  Canvas bytes outside the addressed tiles are not written.
+ * mode SG2_U8_TRUNC (lo, hi ignored): v = x * 127.5f rounded to f32, then + 128.0f rounded to f32 (two roundings,
+ *   never an FMA), clamped to [0, 255], truncated toward zero: bitwise the torch composition
+ *   (x.float() * 127.5 + 128).clamp(0, 255).to(uint8).
+ * mode SG2_U8_RINT: v = (x - (float)lo) * (float)(255.0 / (hi - lo)) (the quotient in double, cast once; a subtract
+ *   and a multiply, two roundings), rounded half to even, clipped to [0, 255]: bitwise numpy's
+ *   rint((x - lo) * (255 / (hi - lo))).clip(0, 255) on a float32 array.  lo, hi finite, hi != lo.
+ * Both modes, by this build's definition (the torch and numpy casts of NaN are undefined): NaN -> 0, +inf -> 255,
+ *   -inf -> 0.
+ * One read of img, one write of the canvas, no scratch, no atomics, 64-bit offsets; 16-byte loads and stores per lane
+ * when Cout = 1, W % 16 == 0 and both bases are 16-byte aligned, aligned 4-byte stores otherwise. */
+#define SG2_TILES_HWC (-1)
+#define SG2_TILES_GREY (-2)
+#define SG2_U8_TRUNC 0
+#define SG2_U8_RINT 1
+int sg2_image_tiles_u8(uint8_t* canvas, const void* img, int dtype, int N, int C, int H, int W, int tiles, int mode,
+                       double lo, double hi, int gw, int gh, int64_t first_tile, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
