@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SG2HIP_LIB', os.path.join(_HERE, 'libsg2hip.so'))
 
 F32, F16, BF16, F32S3 = 0, 1, 2, 3
+U8 = 4      # SG2_U8: sg2_power_spectrum_sum's uint8 images
 _DTYPES = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
 _c_i64p = ctypes.POINTER(ctypes.c_int64)
@@ -101,6 +102,9 @@ SIGNATURES = {
     'sg2_poly_mmd_sums': [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _i64, _vp],
     # (additive to ABI 11: the generator's output stage, images -> uint8 canvas tiles, csrc/imgout.hip)
     'sg2_image_tiles_u8': [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _i, _i, _i64, _vp],
+    # (additive to ABI 11: the summed power spectrum of an image batch, a pruned DFT on the f64 MFMA, csrc/spectrum.hip)
+    'sg2_power_spectrum_scratch_bytes': [_c_i64p, _i, _i, _i, _i],
+    'sg2_power_spectrum_sum': [_vp, _vp, _i, _c_i64p, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 ABI_VERSION = 11
 

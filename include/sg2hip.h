@@ -510,6 +510,30 @@ int sg2_poly_mmd_sums(double* sums, const float* gen, int64_t n_gen, const float
 int sg2_image_tiles_u8(uint8_t* canvas, const void* img, int dtype, int N, int C, int H, int W, int tiles, int mode,
                        double lo, double hi, int gw, int gh, int64_t first_tile, void* stream);
 
+/* The summed 2-D power spectrum of a batch of windowed, zero-padded images (SG3/avg_spectra.py:164-166 summed over the
+ * batch and kept per channel; csrc/spectrum.hip).  ADDITIVE entry points: SG2_ABI_VERSION stays 11.
+ *
+ *   out[c, u, v] = sum_b | sum_{y, x} ((img[b, c, y, x] - mean[c]) / std[c]) w[y] w[x]
+ *                                     exp(-2 pi i (u y + v x) / S) |^2,     S = N * interp,  u, v in [0, S)
+ * out f64 [C, S, S] contiguous, WRITTEN (not accumulated), every element exactly once per call.
+ * img [B, C, N, N] of dtype SG2_U8 or SG2_F32 with element strides[4] = [sB, sC, sY, sX] (any view); window f64 [N],
+ * mean and std f64 [C] (std > 0 is the caller's to check), twiddle: S complex f64 values (re, im interleaved),
+ * twiddle[k] = exp(-2 pi i k / S), computed by the caller in f64 or better and conjugate-symmetric bit for bit
+ * (twiddle[S - k] = conj(twiddle[k]), twiddle[0] = 1, twiddle[S / 2] = -1): the bitwise Hermitian symmetry of out
+ * on the lines v = 0 and v = S / 2 rests on it.  All DEVICE pointers.
+ * A pruned DFT as two f64 MFMA GEMMs with K = N: the padding's zeros are never multiplied, no S x S complex spectrum
+ * is stored (scratch holds the half-transformed [B, C, 2, N, ~S / 2 + 1] f64 rows and one f64 [C, S, S / 2 + 1] sum
+ * per batch group).  Every sum's order depends on (B, C, N, interp) alone, there are no atomics: two calls give the
+ * same bits.  Every scratch element the call reads it has written itself.
+ * N a multiple of 4 in 8..1024, interp >= 1, S <= 4096, B >= 1, C >= 1, B * C <= 65535; anything else, a null
+ * pointer or a short scratch is an argument error and nothing is launched.  3 launches.
+ * sg2_power_spectrum_scratch_bytes: the scratch the call needs. */
+#define SG2_U8 4
+int sg2_power_spectrum_scratch_bytes(int64_t* bytes, int B, int C, int N, int interp);
+int sg2_power_spectrum_sum(double* out, const void* img, int dtype, const int64_t* strides, int B, int C, int N,
+                           int interp, const double* window, const double* mean, const double* std,
+                           const double* twiddle, void* scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
