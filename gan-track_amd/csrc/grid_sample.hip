@@ -297,9 +297,9 @@ int gs_bwd(float* gin, const void* gout, const float* grid, const float* theta, 
     const int64_t extent = (p.N - 1) * p.is_n + (p.C - 1) * p.is_c + (p.Hi - 1) * p.is_h + (p.Wi - 1) * p.is_w + 1;
     hipStream_t s = as_stream(stream);
     const bool gather = det_on() && theta;
+    SG2_CHECK(!gather || p.C <= 4, "sg2_affine_grid_sample_bwd: deterministic mode supports C <= 4");   // before any launch
     if (dyn_hw && gather) {
         // the deterministic gather writes every element of the region below (its band included): no zeroing
-        SG2_CHECK(p.C <= 4, "sg2_affine_grid_sample_bwd: deterministic mode supports C <= 4");
     } else if (dyn_hw) {
         // only the region a consumer of the dynamically sized gradient reads: the logical image plus a
         // band (upfirdn2d.hip kZeroBand and the adjoint FIR's reach)
@@ -317,7 +317,6 @@ int gs_bwd(float* gin, const void* gout, const float* grid, const float* theta, 
     if (total == 0 || p.C == 0) return 0;
     SG2_CHECK(total < INT32_MAX && (int64_t)p.N * p.Hi * p.Wi < INT32_MAX, "sg2_grid_sample_bwd: too many pixels");
     if (gather) {
-        SG2_CHECK(p.C <= 4, "sg2_affine_grid_sample_bwd: deterministic mode supports C <= 4");
         const int64_t tot_in = (int64_t)p.N * p.Hi * p.Wi;
         static const int gmax = [] { const char* e = getenv("SG2_GATHER_GRID"); return e ? atoi(e) : 256 * 64; }();
         const int gi = (int)std::min<int64_t>(cdiv(tot_in, 256), gmax);

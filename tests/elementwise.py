@@ -155,14 +155,20 @@ def min_dropped_term_ratio(g, x_tap, bound):
     return worst
 
 
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
 def _upfirdn(x, f, up, down, padding, flip_filter):
+    """up / down: one factor for both axes, or (x, y) as the separable passes of a 1-D filter need them."""
     N, C, H, W = x.shape
+    (upx, upy), (downx, downy) = _pair(up), _pair(down)
     px0, px1, py0, py1 = [padding] * 4 if isinstance(padding, int) else padding
-    x = F.pad(x.reshape(N, C, H, 1, W, 1), [0, up - 1, 0, 0, 0, up - 1]).reshape(N, C, H * up, W * up)
+    x = F.pad(x.reshape(N, C, H, 1, W, 1), [0, upx - 1, 0, 0, 0, upy - 1]).reshape(N, C, H * upy, W * upx)
     x = F.pad(x, [max(px0, 0), max(px1, 0), max(py0, 0), max(py1, 0)])
     x = x[:, :, max(-py0, 0):x.shape[2] - max(-py1, 0), max(-px0, 0):x.shape[3] - max(-px1, 0)]
     f = f if flip_filter else f.flip([0, 1])
-    return F.conv2d(x, f[None, None].repeat(C, 1, 1, 1), groups=C)[:, :, ::down, ::down]
+    return F.conv2d(x, f[None, None].repeat(C, 1, 1, 1), groups=C)[:, :, ::downy, ::downx]
 
 
 def fir_ref(x, f, dtype, up=1, down=1, padding=0, flip_filter=False, gain=1):
@@ -176,3 +182,104 @@ def fir_ref(x, f, dtype, up=1, down=1, padding=0, flip_filter=False, gain=1):
     xd = x.to(dtype).double()
     kw = dict(up=up, down=down, padding=padding, flip_filter=flip_filter)
     return _upfirdn(xd, fg, **kw), accumulation_slack(f.numel(), _upfirdn(xd.abs(), fg.abs(), **kw))
+
+
+# ------------------------------------------------------------------ the ADA geometric kernels (test_ada_geom_gpu.py)
+def assert_regions(got, computed, band, what, ref=None, slack=None, out_dtype=torch.float32, exact=False):
+    """The three regions of a buffer that is partial by contract (got [N, C, H, W], poisoned with NaN before the
+    kernel ran): rows < computed[0] and cols < computed[1] hold `ref` (bitwise when `exact`, else within the
+    elementwise bound); the rest of rows < band[0], cols < band[1] is exactly 0.0; everything else is still NaN,
+    i.e. was never stored.  Extents beyond the buffer clamp to it.  -> the worst error / bound ratio."""
+    g = got.detach().cpu()
+    H, W = g.shape[2:]
+    cy, cx, by, bx = min(computed[0], H), min(computed[1], W), min(band[0], H), min(band[1], W)
+    rows, cols = torch.arange(H)[:, None], torch.arange(W)[None]
+    in_c = (rows < cy) & (cols < cx)
+    in_b = (rows < by) & (cols < bx) & ~in_c
+    rest = ~(in_c | in_b)
+    nz = int((g[:, :, in_b] != 0).sum())            # NaN != 0 is true: a NaN left in the band counts
+    assert nz == 0, f'{what}: {nz} of {g[:, :, in_b].numel()} zero-band elements (out to {by} x {bx}) are not 0.0'
+    nw = int((~torch.isnan(g[:, :, rest])).sum())
+    assert nw == 0, f'{what}: {nw} elements beyond the band ({by} x {bx} of {H} x {W}) were stored'
+    sub = g[:, :, :cy, :cx]
+    if exact:
+        r = _f64(ref)[:, :, :cy, :cx]
+        nd = int((sub.double() != r).sum())
+        assert nd == 0, f'{what}: {nd} of {sub.numel()} elements of the computed region differ (bitwise)'
+        return 0.0
+    return assert_elementwise(sub, _f64(ref)[:, :, :cy, :cx], torch.as_tensor(slack)[:, :, :cy, :cx], out_dtype, what)
+
+
+def reflect_pad_adjoint_ref(gy, hw, margins):
+    """(ref, slack) of the adjoint of F.pad(x, reflect) for gy [N, C, Hd, Wd] float64 (the padded image's gradient,
+    cropped): the float64 autograd gradient.  A source pixel sums at most 3 x 3 padded positions in f32: at most 8
+    additions (9 with the accumulator's zero), each rounding a partial sum that the same adjoint of |gy| bounds."""
+    mx0, my0, mx1, my1 = margins
+    x = torch.zeros([*gy.shape[:2], *hw], dtype=torch.float64, requires_grad=True)
+    y = F.pad(x, (mx0, mx1, my0, my1), mode='reflect')
+    assert y.shape == gy.shape, (y.shape, gy.shape)
+    ref, = torch.autograd.grad(y, [x], gy, retain_graph=True)
+    mag, = torch.autograd.grad(y, [x], gy.abs())
+    return ref, 8 * EPS32 * mag
+
+
+AFFINE_F32_OPS = 8      # roundings of t0 bx + t1 by + t2 and of base_coord, per unit of |t0| + |t1| + |t2| (below)
+
+
+def grid_sample_ref(x, grid, theta=None):
+    """(ref, slack) of the bilinear sample (zeros padding, align_corners = False) of x [N, C, H, W] float64 (the
+    rounded operands) at grid [N, Ho, Wo, 2] float64 (the f32 grid the kernel reads, or affine_grid of the f32 theta
+    in float64).  grid_sample.hip corners_g forms ix = ((g + 1) W - 1) / 2 in f32: an add, a product and a
+    subtraction (the halving is exact), each rounding a value <= (|g| + 1) W, and the weight differences ix - fx,
+    (fx + 1) - ix one more: 4 roundings, dix = 4 2^-24 (|gx| + 1) W, diy likewise with H.  With `theta` (the
+    in-kernel affine grid) g itself is rounded: base_coord (a division and a subtraction of values <= 2, 3 2^-24
+    absolute), two products and two sums of values <= |t0| + |t1| + |t2|: under AFFINE_F32_OPS = 8 roundings of
+    that sum, times W / 2 in ix.  A coordinate error d moves a bilinear value by at most d times the largest
+    difference of neighbouring pixels, <= 2 M with M the largest |x| in the 5 x 5 pixels around floor(ix, iy) (zero
+    outside the image; two pixels each way cover a floor that d moved across a boundary).  The four products and
+    three additions of the f32 sum: 8 2^-24 S, S the same sample of |x|.  The output type's rounding is
+    assert_elementwise's own u |ref| term."""
+    N, C, H, W = x.shape
+    Ho, Wo = grid.shape[1:3]
+    kw = dict(mode='bilinear', padding_mode='zeros', align_corners=False)
+    ref = F.grid_sample(x, grid, **kw)
+    S = F.grid_sample(x.abs(), grid, **kw)
+    gx, gy = grid[..., 0], grid[..., 1]
+    dx = 4 * EPS32 * (gx.abs() + 1) * W
+    dy = 4 * EPS32 * (gy.abs() + 1) * H
+    if theta is not None:
+        t = theta.double().abs().sum(2)                            # [N, 2]
+        dx = dx + AFFINE_F32_OPS * EPS32 * t[:, 0, None, None] * W / 2
+        dy = dy + AFFINE_F32_OPS * EPS32 * t[:, 1, None, None] * H / 2
+    x0 = (((gx + 1) * W - 1) / 2).floor().clamp(-3, W + 2).long() + 3
+    y0 = (((gy + 1) * H - 1) / 2).floor().clamp(-3, H + 2).long() + 3
+    m = F.max_pool2d(F.pad(x.abs(), [3, 3, 3, 3]), 5, 1, 2)        # [N, C, H + 6, W + 6]: max |x| over 5 x 5
+    idx = (y0 * (W + 6) + x0).view(N, 1, -1).expand(N, C, -1)
+    M = m.flatten(2).gather(2, idx).view(N, C, Ho, Wo)
+    return ref, 2 * (dx + dy)[:, None] * M + 8 * EPS32 * S
+
+
+def grid_sample_grad_ref(x_shape, grid, dy):
+    """(ref, tol) of grid_sample's input gradient for dy [N, C, Ho, Wo] float64: the float64 autograd gradient and
+    the bound of test_det_gather_matches_scatter_ada_maps, 2^-11 (the same gradient of |dy| + max |dy|)."""
+    x = torch.zeros(x_shape, dtype=torch.float64, requires_grad=True)
+    y = F.grid_sample(x, grid, mode='bilinear', padding_mode='zeros', align_corners=False)
+    ref, = torch.autograd.grad(y, [x], dy, retain_graph=True)
+    mag, = torch.autograd.grad(y, [x], dy.abs())
+    return ref, 2.0 ** -11 * (mag + float(dy.abs().max()))
+
+
+def fir_chain_ref(x, passes, dtype=torch.float32):
+    """(ref, slack) of FIR passes run one after the other (a separable filter's horizontal and vertical launch), each
+    a dict(f=2-D filter, up, down, padding, flip_filter, gain) as fir_ref takes them.  The reference is the float64
+    chain; a pass's slack is the previous slack pushed through its |taps| plus its own accumulation slack on the
+    operand it really meets (|previous reference| + previous slack).  Nothing rounds between f32 passes."""
+    ref = x if x.dtype == torch.float64 else x.to(dtype).double()     # (float64: taken as already rounded)
+    slack = torch.zeros_like(ref)
+    for p in passes:
+        fg = (p['f'].float() * torch.tensor(p.get('gain', 1), dtype=torch.float32)).double()
+        kw = dict(up=p.get('up', 1), down=p.get('down', 1), padding=p.get('padding', 0),
+                  flip_filter=p.get('flip_filter', False))
+        slack = _upfirdn(slack, fg.abs(), **kw) + accumulation_slack(fg.numel(), _upfirdn(ref.abs() + slack, fg.abs(), **kw))
+        ref = _upfirdn(ref, fg, **kw)
+    return ref, slack

@@ -26,6 +26,10 @@ extent is read) or are not established to hold floats only:
     upfirdn2d._raw_lim and grid_sample_gradfix._Bwd with dyn_hw: these share a module with fully written outputs, so
     the proxy stays off upfirdn2d and grid_sample_gradfix in the tests that drive the dynamic-extent route
     (DYNAMIC_EXTENT_TESTS), and inside `unpoisoned` for the dyn_hw call of test_affine_grid_sample.
+The partial-by-contract buffers are checked in tests/test_ada_geom_gpu.py instead: there each test poisons
+reflect_pad, upfirdn2d and grid_sample_gradfix in its own body and holds every kernel of the ADA geometric chain to
+three regions -- computed within its bound, zero band exactly 0.0, the rest still NaN -- and feeds each consumer its
+input as the producer leaves it (tests/ada_regions.py; the region arithmetic alone in test_ada_geom_host.py).
 """
 import contextlib
 import importlib
