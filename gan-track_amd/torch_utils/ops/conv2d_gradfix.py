@@ -488,8 +488,10 @@ def vjp_axpy(a, sa=None, b=None, sb=None, y=None, act=0, alpha=0.2, gain=1.0, cl
         return _nhwc(v.to(a.dtype)), dot
     a = _nhwc(a)
     args = [_nhwc(t) if t is not None else None for t in (b, y, e)]
-    for t in args:
-        assert t is None or (t.shape == a.shape and t.dtype == a.dtype), 'vjp_axpy: operand shape / dtype'
+    for t in args:   # (the kernel sizes every buffer from a: a mismatch must not reach it, under `python -O` either)
+        if t is not None and (t.shape != a.shape or t.dtype != a.dtype):
+            raise RuntimeError(f'vjp_axpy: operand shape / dtype {tuple(t.shape)} {t.dtype} differs from a: '
+                               f'{tuple(a.shape)} {a.dtype}')
     b, y, e = args
     sa = sa.float().contiguous() if sa is not None else None
     sb = sb.float().contiguous() if sb is not None else None

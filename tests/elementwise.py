@@ -283,3 +283,220 @@ def fir_chain_ref(x, passes, dtype=torch.float32):
         slack = _upfirdn(slack, fg.abs(), **kw) + accumulation_slack(fg.numel(), _upfirdn(ref.abs() + slack, fg.abs(), **kw))
         ref = _upfirdn(ref, fg, **kw)
     return ref, slack
+
+
+# ------------------------------------------------------------------ the layer-backward kernels (test_layer_bwd_gpu.py)
+# layer_bwd.hip: sg2_layer_bwd, sg2_dot_hw and sg2_vjp_axpy share one lane layout.  A lane owns 8 channels of a pixel,
+# LP = C / 8 lanes cover a pixel, PPP = 256 // LP pixels are in flight per pass (threads beyond LP PPP idle), and a
+# workgroup owns min(HW, passes PPP) pixels: passes = 16 in layer_bwd and vjp_axpy, 32 in dot_hw.
+LB_CS = (8, 24, 64, 96, 512, 520, 1024, 2048)       # LP 1, 3, 8, 12, 64, 65, 128, 256: every path of the layout
+LB_BOUND_CS = (24, 64, 1024)                        # the three noise routes: LDS (no power of two), shuffle, LDS (> 64)
+LB_NS = (1, 3)
+LB_EXACT = dict(alpha=0.25, gain=2.0, clamp=2.5)    # powers of two (and a clamp on the y grid): every product exact
+LB_QUANTUM = 0.5                                    # every term of every reduction of the exact fixture is k / 2
+
+
+def f32(v):
+    """A Python scalar as the kernel receives it (a float argument)."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def gamma(k):
+    """k f32 roundings in a row: (1 + 2^-24)^k - 1 <= k 2^-24 / (1 - k 2^-24)."""
+    return k * EPS32 / (1 - k * EPS32)
+
+
+def lb_layout(C, passes=16):
+    """(LP, PPP, pixels per workgroup at HW -> infinity)."""
+    LP = C // 8
+    PPP = 256 // LP
+    return LP, PPP, passes * PPP
+
+
+def lb_hws(C, passes=16):
+    """One pixel; a second pass of one pixel; exactly one workgroup; a second workgroup of one pixel; several
+    workgroups with a tail that is no multiple of the 4 PPP pixels a lane keeps in flight."""
+    _, PPP, ppb = lb_layout(C, passes)
+    return [1, PPP + 1, ppb, ppb + 1, 37 * PPP + 5]
+
+
+def lb_exact_operands(N, C, HW):
+    """Operands (float64 [N, C, HW, 1] and [N, C]) whose every product and partial sum in the three kernels is exact
+    in f32 and whose every elementwise result is a bf16 (hence fp16, f32) value: small integers, halves for y (so
+    y == 0 and |y| == clamp are frequent), powers of two for the per-(sample, channel) factors.  A dropped, doubled or
+    misrouted term then is a bitwise mismatch in any summation order.  lb_assert_exact checks the precondition."""
+    g = torch.Generator().manual_seed(1000003 * C + 101 * HW + N)
+    shape = (N, C, HW, 1)
+
+    def ints(lo, hi, *s):
+        return torch.randint(lo, hi + 1, s, generator=g).double()
+
+    def pow2(*s):
+        return 2.0 ** ints(-1, 2, *s)
+    op = dict(dy=ints(-8, 8, *shape), c=ints(-8, 8, *shape), y=ints(-6, 6, *shape) / 2, a=ints(-8, 8, *shape),
+              b=ints(-8, 8, *shape), e=ints(-8, 8, *shape), d=pow2(N, C), sa=pow2(N, C))
+    op['sb'] = pow2(N, C) * (ints(0, 1, N, C) * 2 - 1)
+    return op
+
+
+def lb_random_operands(N, C, HW, dtype, seed=0):
+    """Random normal operands rounded to `dtype` (float64 values): y scaled by 2 so that a clamp of 2.5 masks some."""
+    g = torch.Generator().manual_seed(7919 * C + 13 * HW + N + seed)
+    shape = (N, C, HW, 1)
+    op = {k: rnd(torch.randn(shape, generator=g), dtype) for k in ('dy', 'c', 'a', 'b', 'e')}
+    op['y'] = rnd(torch.randn(shape, generator=g) * 2, dtype)
+    op['d'] = (torch.rand(N, C, generator=g) + 0.5).float().double()
+    op['sa'] = (torch.rand(N, C, generator=g) + 0.5).float().double()
+    op['sb'] = torch.randn(N, C, generator=g).float().double()
+    return op
+
+
+def _act_grad(v, y, act, alpha, gain, clamp):
+    """bias_act's first-order gradient factor as the kernels apply it: v gain [alpha where not y > 0] and then
+    ASSIGNED 0 where not -clamp < y < clamp (strict; a NaN y fails both comparisons, so it takes alpha and, with a
+    clamp, gives exactly 0 whatever v holds).  -> (value, |value| with the same mask)."""
+    alpha, gain, clamp = f32(alpha), f32(gain), f32(clamp)
+    v, m = v * gain, v.abs() * abs(gain)
+    if act == 1:
+        pos = y > 0
+        v, m = torch.where(pos, v, v * alpha), torch.where(pos, m, m * abs(alpha))
+    if clamp >= 0:
+        keep = (y > -clamp) & (y < clamp)
+        v, m = torch.where(keep, v, torch.zeros_like(v)), torch.where(keep, m, torch.zeros_like(m))
+    return v, m
+
+
+def layer_bwd_ref(dy, y, c=None, d=None, act=1, alpha=0.2, gain=1.0, clamp=-1.0):
+    """sg2_layer_bwd in float64 (operands float64 [N, C, H, W], d [N, C]): dz = act'(dy; y), dc = dz d, db = sum_{n,p}
+    dz, dd = sum_p dz c, dnoise = sum_c dz, and under 'A_*' the same reductions of |terms|."""
+    dz, mz = _act_grad(dy, y, act, alpha, gain, clamp)
+    r = dict(dz=dz, dc=dz * d[:, :, None, None] if d is not None else dz, db=dz.sum([0, 2, 3]), A_db=mz.sum([0, 2, 3]),
+             dnoise=dz.sum(1, keepdim=True), A_dnoise=mz.sum(1, keepdim=True))
+    if c is not None:
+        r['dd'], r['A_dd'] = (dz * c).sum([2, 3]), (mz * c.abs()).sum([2, 3])
+    return r
+
+
+def vjp_axpy_ref(a, sa=None, b=None, sb=None, y=None, act=0, alpha=0.2, gain=1.0, clamp=-1.0, e=None):
+    """sg2_vjp_axpy in float64: out = act'(a sa + b sb; y) (act' only with y), dot = sum_p a e; 'mag' is the same
+    expression of the operands' absolute values (what the f32 roundings before the output's own are relative to),
+    'A_dot' the sum of |a e|."""
+    v = a * (sa[:, :, None, None] if sa is not None else 1.0)
+    m = v.abs()
+    if b is not None:
+        t = b * (sb[:, :, None, None] if sb is not None else 1.0)
+        v, m = v + t, m + t.abs()
+    if y is not None:
+        v, _ = _act_grad(v, y, act, alpha, gain, clamp)
+        m, _ = _act_grad(m, y, act, abs(alpha), abs(gain), clamp)
+    r = dict(out=v, mag=m)
+    if e is not None:
+        r['dot'], r['A_dot'] = (a * e).sum([2, 3]), (a * e).abs().sum([2, 3])
+    return r
+
+
+def dot_hw_ref(a, b, dtype):
+    """sg2_dot_hw in float64: sum_p round(a b), the product rounded to the operands' type as torch's `a * b` does
+    (exact in f32 for 16-bit operands, so one rounding) -> (dot, the same sum of |terms|)."""
+    t = (a.float() * b.float()).to(dtype).double()
+    return t.sum([2, 3]), t.abs().sum([2, 3])
+
+
+def det_sum_depth(S, n, G=1):
+    """The longest chain of f32 additions through det.hip's det_sum over S slots of n outputs (G groups): four lane
+    rows sum every fourth slot in order, ceil(S / 4) additions, the rows are added in order (4 with the zero start);
+    few outputs over a long sum go through K chunks first (the same form twice).  The sequential form it takes at
+    S <= 16 over many outputs is S additions.  One more for the final add into the output."""
+    cdiv = lambda p, q: -(-p // q)      # noqa: E731
+    bx = cdiv(n, 64)
+    K = 1
+    if bx * G < 512 and S > 64:
+        K = min(cdiv(S, 64), 1024, cdiv(512, bx * G))
+    if K > 1:
+        chunk = cdiv(S, K)
+        K = cdiv(S, chunk)
+        return cdiv(chunk, 4) + 4 + cdiv(K, 4) + 4 + 1
+    return max(cdiv(S, 4) + 4, S if S <= 16 else 0) + 1
+
+
+def lb_depths(C, HW, N, det, passes=16):
+    """The longest chain of f32 additions any contribution passes through, per output, read from layer_bwd.hip:
+
+    per thread   a lane adds the pixels p0 + pl + k PPP of its workgroup into a register, k < passes: `passes` adds
+                 (16 in layer_bwd_kernel and vjp_axpy_kernel, 32 in dot_hw_kernel; the U = 4 unroll keeps the order);
+    workgroup    atomic mode: the PPP lanes of a channel atomicAdd into the LDS cell: PPP additions in any order;
+                 deterministic mode: det_rows_sum adds the PPP rows in order: PPP additions;
+    grid         db: one contribution per workgroup, gridDim.x N of them; dd and dot: gridDim.x per sample.  Atomic
+                 mode: that many global atomicAdds (plus the memset's zero: no rounding); deterministic mode: det_sum
+                 over that many slots (det_sum_depth), which also covers the add into a caller's accumulator;
+    dnoise       never leaves the workgroup: 8 additions for the lane's channels, then log2 LP shuffle steps (LP a
+                 power of two <= 64), else LP LDS atomicAdds, or LP ordered additions of the dn_part partials."""
+    LP, PPP, ppb = lb_layout(C, passes)
+    grid = -(-HW // min(HW, ppb))
+    step = (lambda S, n: det_sum_depth(S, n)) if det else (lambda S, n: S + 1)
+    shfl = LP & (LP - 1) == 0 and LP <= 64
+    return dict(db=passes + PPP + step(grid * N, C), dd=passes + PPP + step(grid, N * C),
+                dot=passes + PPP + step(grid, N * C), dnoise=8 + (LP.bit_length() - 1 if shfl else LP))
+
+
+def layer_bwd_slack(ref, C, HW, N, det):
+    """Judge 2 of sg2_layer_bwd -> slack per output.  dz = (dy gain) alpha: 2 f32 roundings; dc = dz d: a third, and
+    that is all before the output's own rounding (for an f32 output the third IS the output's): gamma(3) |dc|.
+    The reductions are f32 outputs: a term carries t roundings (dz: 2; dz c: 3, or 2 where the compiler contracts
+    the product into an FMA) and then passes through `depth` additions (lb_depths), each rounding a partial sum that
+    the same reduction of |terms|, A, bounds: gamma(t + depth) A."""
+    dep = lb_depths(C, HW, N, det)
+    s = dict(dc=gamma(3) * ref['dc'].abs(), db=gamma(2 + dep['db']) * ref['A_db'],
+             dnoise=gamma(2 + dep['dnoise']) * ref['A_dnoise'])
+    if 'dd' in ref:
+        s['dd'] = gamma(3 + dep['dd']) * ref['A_dd']
+    return s
+
+
+def vjp_axpy_slack(ref, C, HW, N, det):
+    """Judge 2 of sg2_vjp_axpy.  out: v = a sa (1 rounding), fmaf(b, sb, v) (1), v gain (1), v alpha (1): 4 f32
+    roundings, each of a value that 'mag' (the expression of the absolute values) bounds, before the one rounding to
+    the output type -- gamma(4) mag (for an f32 output the cast rounds nothing, so the four are all there is).
+    dot: acc = fmaf(a, e, acc) -- the product is not rounded (t = 0), every addition is: gamma(depth) A."""
+    s = dict(out=gamma(4) * ref['mag'])
+    if 'dot' in ref:
+        s['dot'] = gamma(lb_depths(C, HW, N, det)['dot']) * ref['A_dot']
+    return s
+
+
+def dot_hw_slack(A, C, HW, N, det):
+    """Judge 2 of sg2_dot_hw: the terms are the rounded products (in the reference too: t = 0); 32 passes a lane."""
+    return gamma(lb_depths(C, HW, N, det, passes=32)['dot']) * A
+
+
+def lb_assert_exact(sums, elementwise):
+    """The precondition of Judge 1, on the reference alone: sums = [(name, A)] with A the float64 sum of |terms| of a
+    reduction -- A / quantum below 2^24, so every partial sum in any order is an f32 value; elementwise = [(name,
+    float64 tensor)] -- every value survives a round trip through bf16 and fp16."""
+    for name, A in sums:
+        assert float(A.max()) / LB_QUANTUM < 2 ** 24, (name, float(A.max()))
+        assert torch.equal(A / LB_QUANTUM, (A / LB_QUANTUM).round()), f'{name}: a term off the {LB_QUANTUM} grid'
+    for name, v in elementwise:
+        for dt in (torch.bfloat16, torch.float16):
+            assert torch.equal(v.to(dt).double(), v), f'{name}: not exact in {dt}'
+
+
+def lb_judge_exact(got, ref, what):
+    """Judge 1: every output of `got` (name -> tensor, any device / dtype) bitwise the float64 reference.  NaN never
+    equals, so an element that was not stored fails too."""
+    for k, v in got.items():
+        g, r = _f64(v), ref[k]
+        assert tuple(g.shape) == tuple(r.shape), (what, k, tuple(g.shape), tuple(r.shape))
+        if not torch.equal(g, r):
+            bad = (g != r).nonzero()
+            at = tuple(bad[0].tolist())
+            raise AssertionError(f'{what} {k}: {bad.shape[0]} of {g.numel()} elements differ from the exact reference, '
+                                 f'first at {at}: got {g[at].item()!r}, ref {r[at].item()!r}; last at '
+                                 f'{tuple(bad[-1].tolist())} (index order of shape {tuple(g.shape)})')
+
+
+def lb_judge_bound(got, ref, slack, dtype, what):
+    """Judge 2: every element of every output within its derived bound -> {name: worst error / bound}.  The
+    elementwise outputs ('dc', 'out') are `dtype` values, the reductions f32."""
+    return {k: assert_elementwise(v, ref[k], slack[k], dtype if k in ('dc', 'out') else torch.float32, f'{what} {k}')
+            for k, v in got.items()}

@@ -254,6 +254,9 @@ def test_det_dot_hw_and_vjp_axpy():
     a = _nhwc(torch.randn(3, 64, 37, 41, generator=g), torch.float16)
     b = _nhwc(torch.randn(3, 64, 37, 41, generator=g), torch.float16)
     _check(lambda: [cg.dot_hw(a, b)], 1e-5)
+    # vjp_axpy's dot goes through per-workgroup slots too (the form of modconv._LayerVJP: G and sum_p g_dx * dxs)
+    sa, sb = (torch.rand(3, 64, generator=g) + 0.5).to(DEV), torch.randn(3, 64, generator=g).to(DEV)
+    _check(lambda: list(cg.vjp_axpy(a, sa, b, sb, e=b)), 1e-5)
 
 
 @pytest.mark.timeout(300)
