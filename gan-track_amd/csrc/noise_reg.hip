@@ -14,12 +14,16 @@
 //   normalize = 1 launch, a workgroup per buffer, three passes over L2-resident data.
 // Every sum is a fixed tree (no atomics): <= 16-term serial runs per lane, wave butterflies, LDS across waves,
 // then <= 16-term runs over chunk partials.  Two calls on the same input give the same bits.
+// The *_batched entry points run the same kernel bodies over B samples per buffer (buffer-major: sample s of buffer b
+// at off[b] + s R^2), the sample being the grid's y: the launch counts do not grow with B, every sample has its own
+// share of the scratch, and a sample's results are bitwise those of the batch-1 entry points on its buffers alone.
 #include "sg2_common.h"
 
 namespace sg2 {
 namespace {
 
 constexpr int NR_MAXBUF = 32;
+constexpr int NR_MAXBATCH = 64;     // samples of the batched entry points (a grid dimension)
 constexpr int NR_CHUNK = 1024;      // elements per corr / bwd workgroup (256 threads x float4)
 constexpr int NR_MAXLEV = 8;        // R = 1024: 1024, 512, ..., 8
 
@@ -77,23 +81,26 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     return t[0];
 }
 
+// Every kernel body below is a device function of (argument block, workgroup index, sample): the batch-1 kernels call
+// it with sample 0 and the batched ones with blockIdx.y and that sample's scratch, so both run one code and one tree.
+// Sample s of buffer b lies at flat + off[b] + s R^2 (the buffer-major layout of make_batched_table).
+
 // ---- pool: thread (ly, lx) of a 16 x 16 workgroup owns a P x P patch of level 0, pools it in registers down to one
 // value (levels 1 .. log2 P), then the workgroup pools its 16 x 16 values through LDS (4 more levels).  P = 4 reaches
 // level 6 (R <= 512), P = 8 level 7 (R = 1024).
 template <int P>
-__global__ __launch_bounds__(256) void nr_pool_kernel(NrArgs a, const float* __restrict__ flat,
-                                                      float* __restrict__ scratch) {
+__device__ __forceinline__ void nr_pool_body(const NrArgs& a, int blk, int64_t samp, const float* __restrict__ flat,
+                                             float* __restrict__ scratch, float (*lds)[256]) {
     constexpr int TILE = 16 * P, KP = P == 4 ? 2 : 3;
-    __shared__ float lds[2][256];
-    const int b = nr_find(a.pool_blk, a.nbuf, blockIdx.x);
-    const int t = blockIdx.x - a.pool_blk[b];
+    const int b = nr_find(a.pool_blk, a.nbuf, blk);
+    const int t = blk - a.pool_blk[b];
     const int R = a.R[b], nlev = a.nlev[b];
     const int tiles_x = R > TILE ? R / TILE : 1;
     const int ty = t / tiles_x, tx = t % tiles_x;
     const int tid = threadIdx.x, lx = tid & 15, ly = tid >> 4;
     const int x0 = tx * TILE + lx * P, y0 = ty * TILE + ly * P;
     const bool active = x0 < R && y0 < R;               // R >= 16 here: a multiple of P
-    const float* src = flat + a.off[b];
+    const float* src = flat + a.off[b] + samp * R * R;
     float* dst = scratch + a.soff[b];
 
     float v[P][P];
@@ -148,17 +155,30 @@ __global__ __launch_bounds__(256) void nr_pool_kernel(NrArgs a, const float* __r
     }
 }
 
-// ---- corr: one 1024-element chunk of one level: sum n[y][x] n[y][x-1] and sum n[y][x] n[y-1][x] (circular) ----
-__global__ __launch_bounds__(256) void nr_corr_kernel(NrArgs a, const float* __restrict__ flat,
+template <int P>
+__global__ __launch_bounds__(256) void nr_pool_kernel(NrArgs a, const float* __restrict__ flat,
                                                       float* __restrict__ scratch) {
-    __shared__ float red[4];
-    const int b = nr_find(a.corr_blk, a.nbuf, blockIdx.x);
-    int c = blockIdx.x - a.corr_blk[b];
+    __shared__ float lds[2][256];
+    nr_pool_body<P>(a, blockIdx.x, 0, flat, scratch, lds);
+}
+
+template <int P>    // grid (pool tiles, B); sstride: floats of scratch per sample
+__global__ __launch_bounds__(256) void nr_pool_batched_kernel(NrArgs a, const float* __restrict__ flat,
+                                                              float* __restrict__ scratch, int64_t sstride) {
+    __shared__ float lds[2][256];
+    nr_pool_body<P>(a, blockIdx.x, blockIdx.y, flat, scratch + blockIdx.y * sstride, lds);
+}
+
+// ---- corr: one 1024-element chunk of one level: sum n[y][x] n[y][x-1] and sum n[y][x] n[y-1][x] (circular) ----
+__device__ __forceinline__ void nr_corr_body(const NrArgs& a, int blk, int64_t samp, const float* __restrict__ flat,
+                                             float* __restrict__ scratch, float* red) {
+    const int b = nr_find(a.corr_blk, a.nbuf, blk);
+    int c = blk - a.corr_blk[b];
     const int R = a.R[b];
     int l = 0;
     while (c >= nr_chunks(R >> l)) { c -= nr_chunks(R >> l); ++l; }     // l < nlev: the prefix counts exactly these
     const int S = R >> l, m = S - 1, n = S * S;
-    const float* p = l == 0 ? flat + a.off[b] : scratch + a.soff[b] + nr_level_off(R, l);
+    const float* p = l == 0 ? flat + a.off[b] + samp * R * R : scratch + a.soff[b] + nr_level_off(R, l);
     const int e = c * NR_CHUNK + (int)threadIdx.x * 4;
     float px = 0.f, py = 0.f;
     if (e < n) {                                        // S % 4 == 0: the four elements share a row
@@ -171,13 +191,24 @@ __global__ __launch_bounds__(256) void nr_corr_kernel(NrArgs a, const float* __r
     }
     px = block_sum<4>(px, red);
     py = block_sum<4>(py, red);
-    if (threadIdx.x == 0) *(float2*)(scratch + a.part_off + 2 * (int64_t)blockIdx.x) = float2{px, py};
+    if (threadIdx.x == 0) *(float2*)(scratch + a.part_off + 2 * (int64_t)blk) = float2{px, py};
+}
+
+__global__ __launch_bounds__(256) void nr_corr_kernel(NrArgs a, const float* __restrict__ flat,
+                                                      float* __restrict__ scratch) {
+    __shared__ float red[4];
+    nr_corr_body(a, blockIdx.x, 0, flat, scratch, red);
+}
+
+__global__ __launch_bounds__(256) void nr_corr_batched_kernel(NrArgs a, const float* __restrict__ flat,
+                                                              float* __restrict__ scratch, int64_t sstride) {
+    __shared__ float red[4];
+    nr_corr_body(a, blockIdx.x, blockIdx.y, flat, scratch + blockIdx.y * sstride, red);
 }
 
 // ---- finalize: one workgroup of 16 waves; a wave per (buffer, level) sums that level's chunk partials ----
-__global__ __launch_bounds__(1024) void nr_finalize_kernel(NrArgs a, float* __restrict__ reg, float* __restrict__ means,
-                                                           const float* __restrict__ scratch) {
-    __shared__ float term[NR_MAXBUF * NR_MAXLEV];
+__device__ __forceinline__ void nr_finalize_body(const NrArgs& a, float* __restrict__ reg, float* __restrict__ means,
+                                                 const float* __restrict__ scratch, float* term) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float2* part = (const float2*)(scratch + a.part_off);
     for (int it = wave; it < a.nitems; it += 16) {
@@ -210,12 +241,28 @@ __global__ __launch_bounds__(1024) void nr_finalize_kernel(NrArgs a, float* __re
     }
 }
 
+__global__ __launch_bounds__(1024) void nr_finalize_kernel(NrArgs a, float* __restrict__ reg, float* __restrict__ means,
+                                                           const float* __restrict__ scratch) {
+    __shared__ float term[NR_MAXBUF * NR_MAXLEV];
+    nr_finalize_body(a, reg, means, scratch, term);
+}
+
+// grid (1, B): sample s writes reg[s] and means[s][nitems][2]
+__global__ __launch_bounds__(1024) void nr_finalize_batched_kernel(NrArgs a, float* __restrict__ reg,
+                                                                   float* __restrict__ means,
+                                                                   const float* __restrict__ scratch, int64_t sstride) {
+    __shared__ float term[NR_MAXBUF * NR_MAXLEV];
+    const int64_t s = blockIdx.y;
+    nr_finalize_body(a, reg + s, means + s * 2 * a.nitems, scratch + s * sstride, term);
+}
+
 // ---- backward: d reg / d n0[y][x] = sum_l 4^-l (2 mx_l / cnt_l (W + E) + 2 my_l / cnt_l (N + S)) of the ancestor ----
-__global__ __launch_bounds__(256) void nr_bwd_kernel(NrArgs a, float* __restrict__ gflat, const float* __restrict__ greg,
-                                                     const float* __restrict__ means, const float* __restrict__ flat,
-                                                     const float* __restrict__ scratch, int accumulate) {
-    const int b = nr_find(a.bwd_blk, a.nbuf, blockIdx.x);
-    const int c = blockIdx.x - a.bwd_blk[b];
+__device__ __forceinline__ void nr_bwd_body(const NrArgs& a, int blk, int64_t samp, float* __restrict__ gflat,
+                                            const float* __restrict__ greg, const float* __restrict__ means,
+                                            const float* __restrict__ flat, const float* __restrict__ scratch,
+                                            int accumulate) {
+    const int b = nr_find(a.bwd_blk, a.nbuf, blk);
+    const int c = blk - a.bwd_blk[b];
     const int R = a.R[b], nlev = a.nlev[b];
     const int e = c * NR_CHUNK + (int)threadIdx.x * 4;
     if (e >= R * R) return;
@@ -225,7 +272,7 @@ __global__ __launch_bounds__(256) void nr_bwd_kernel(NrArgs a, float* __restrict
     float acc[4];
     {
         const int m = R - 1;
-        const float* p = flat + a.off[b];
+        const float* p = flat + a.off[b] + samp * R * R;
         const float2 mm = mean[0];
         const float cnt = (float)(R * R);
         const float cx = 2.f * mm.x / cnt, cy = 2.f * mm.y / cnt;
@@ -257,13 +304,30 @@ __global__ __launch_bounds__(256) void nr_bwd_kernel(NrArgs a, float* __restrict
             else { acc[0] += v; acc[1] += v; acc[2] += v; acc[3] += v; }
         }
     }
-    float4* out = (float4*)(gflat + a.off[b] + e);
+    float4* out = (float4*)(gflat + a.off[b] + samp * R * R + e);
     float4 r = float4{acc[0] * g, acc[1] * g, acc[2] * g, acc[3] * g};
     if (accumulate) {
         const float4 old = *out;
         r.x += old.x; r.y += old.y; r.z += old.z; r.w += old.w;
     }
     *out = r;
+}
+
+__global__ __launch_bounds__(256) void nr_bwd_kernel(NrArgs a, float* __restrict__ gflat, const float* __restrict__ greg,
+                                                     const float* __restrict__ means, const float* __restrict__ flat,
+                                                     const float* __restrict__ scratch, int accumulate) {
+    nr_bwd_body(a, blockIdx.x, 0, gflat, greg, means, flat, scratch, accumulate);
+}
+
+// grid (level-0 chunks, B): sample s reads greg[s], means[s] and its own pooled levels
+__global__ __launch_bounds__(256) void nr_bwd_batched_kernel(NrArgs a, float* __restrict__ gflat,
+                                                             const float* __restrict__ greg,
+                                                             const float* __restrict__ means,
+                                                             const float* __restrict__ flat,
+                                                             const float* __restrict__ scratch, int64_t sstride,
+                                                             int accumulate) {
+    const int64_t s = blockIdx.y;
+    nr_bwd_body(a, blockIdx.x, s, gflat, greg + s, means + s * 2 * a.nitems, flat, scratch + s * sstride, accumulate);
 }
 
 // ---- normalize: a workgroup per buffer; each pass sums float4 groups of 16 per lane, then the groups ----
@@ -288,11 +352,10 @@ __device__ __forceinline__ float nr_grouped_sum(const float4* p, int n4, float m
     return tot + ((acc.x + acc.y) + (acc.z + acc.w));
 }
 
-__global__ __launch_bounds__(1024) void nr_normalize_kernel(NrArgs a, float* __restrict__ flat) {
-    __shared__ float red[16];
-    const int b = blockIdx.x;
+__device__ __forceinline__ void nr_normalize_body(const NrArgs& a, int b, int64_t samp, float* __restrict__ flat,
+                                                  float* red) {
     const int n = a.R[b] * a.R[b], n4 = n / 4;
-    float4* p = (float4*)(flat + a.off[b]);
+    float4* p = (float4*)(flat + a.off[b] + samp * n);
     const float mu = block_sum<16>(nr_grouped_sum<0>(p, n4, 0.f), red) / (float)n;
     const float m2 = block_sum<16>(nr_grouped_sum<1>(p, n4, mu), red) / (float)n;
     const float rs = 1.f / sqrtf(m2);
@@ -303,10 +366,22 @@ __global__ __launch_bounds__(1024) void nr_normalize_kernel(NrArgs a, float* __r
     }
 }
 
+__global__ __launch_bounds__(1024) void nr_normalize_kernel(NrArgs a, float* __restrict__ flat) {
+    __shared__ float red[16];
+    nr_normalize_body(a, blockIdx.x, 0, flat, red);
+}
+
+__global__ __launch_bounds__(1024) void nr_normalize_batched_kernel(NrArgs a, float* __restrict__ flat) {   // grid (nbuf, B)
+    __shared__ float red[16];
+    nr_normalize_body(a, blockIdx.x, blockIdx.y, flat, red);
+}
+
 // ---- host side ----
 // table: HOST int64 [nbuf][2] = (offset of the buffer in flat, in floats; R).  Fills the kernels' argument block.
-int nr_plan(NrArgs& a, const char* what, const int64_t* table, int nbuf) {
+// B: samples per buffer (the batched entry points; a row's buffer then spans B R^2 floats from its offset).
+int nr_plan(NrArgs& a, const char* what, const int64_t* table, int nbuf, int B = 1) {
     const std::string w(what);
+    SG2_CHECK(B >= 1 && B <= NR_MAXBATCH, w + ": B must be in 1..64");
     SG2_CHECK(table, w + ": table must be non-null");
     SG2_CHECK(nbuf >= 1 && nbuf <= NR_MAXBUF, w + ": nbuf must be in 1..32");
     a = NrArgs{};
@@ -318,7 +393,7 @@ int nr_plan(NrArgs& a, const char* what, const int64_t* table, int nbuf) {
         SG2_CHECK(R >= 4 && R <= 1024 && (R & (R - 1)) == 0,
                   w + ": R must be a power of two in 4..1024 (square buffers only)");
         SG2_CHECK(off >= 0 && off % 4 == 0, w + ": buffer offsets must be non-negative multiples of 4 floats");
-        SG2_CHECK(off + R * R <= 0x7fffffffLL / 4, w + ": the flat buffer must stay below 2 GiB");
+        SG2_CHECK(off + B * R * R <= 0x7fffffffLL / 4, w + ": the flat buffer must stay below 2 GiB");
         a.R[b] = (int)R;
         a.nlev[b] = nr_levels((int)R);
         a.off[b] = off;
@@ -342,6 +417,8 @@ int nr_plan(NrArgs& a, const char* what, const int64_t* table, int nbuf) {
 }
 
 int64_t nr_scratch_floats(const NrArgs& a) { return a.part_off + 2 * (int64_t)a.corr_blk[a.nbuf]; }
+// a sample's share of the batched scratch: the batch-1 scratch, rounded up so every share stays 16-byte aligned
+int64_t nr_sample_stride(const NrArgs& a) { return (nr_scratch_floats(a) + 3) / 4 * 4; }
 
 }  // namespace
 }  // namespace sg2
@@ -396,4 +473,59 @@ extern "C" int sg2_noise_normalize_multi(float* flat, const int64_t* table, int 
     SG2_CHECK(((uintptr_t)flat % 16) == 0, "sg2_noise_normalize_multi: flat must be 16-byte aligned");
     nr_normalize_kernel<<<nbuf, 1024, 0, as_stream(stream)>>>(a, flat);
     return launch_status("sg2_noise_normalize_multi");
+}
+
+// ---- the batched entry points: B samples per buffer, the sample a grid dimension; per sample the batch-1 code ----
+extern "C" int sg2_noise_reg_batched_scratch_bytes(int64_t* bytes, const int64_t* table, int nbuf, int B) {
+    SG2_CHECK(bytes, "sg2_noise_reg_batched_scratch_bytes: bytes must be non-null");
+    NrArgs a;
+    if (nr_plan(a, "sg2_noise_reg_batched_scratch_bytes", table, nbuf, B) < 0) return -1;
+    *bytes = nr_sample_stride(a) * B * 4;
+    return 0;
+}
+
+extern "C" int sg2_noise_reg_fwd_batched(float* reg, float* means, const float* flat, const int64_t* table, int nbuf,
+                                         int B, void* scratch, void* stream) {
+    NrArgs a;
+    const int patch = nr_plan(a, "sg2_noise_reg_fwd_batched", table, nbuf, B);
+    if (patch < 0) return -1;
+    SG2_CHECK(reg && means && flat && scratch,
+              "sg2_noise_reg_fwd_batched: reg, means, flat and scratch must be non-null");
+    SG2_CHECK(((uintptr_t)flat % 16) == 0 && ((uintptr_t)scratch % 16) == 0 && ((uintptr_t)means % 8) == 0,
+              "sg2_noise_reg_fwd_batched: flat and scratch must be 16-byte aligned, means 8-byte aligned");
+    hipStream_t s = as_stream(stream);
+    float* sc = (float*)scratch;
+    const int64_t ss = nr_sample_stride(a);
+    if (a.pool_blk[nbuf] > 0) {
+        const dim3 grid(a.pool_blk[nbuf], B);
+        if (patch == 8) nr_pool_batched_kernel<8><<<grid, 256, 0, s>>>(a, flat, sc, ss);
+        else nr_pool_batched_kernel<4><<<grid, 256, 0, s>>>(a, flat, sc, ss);
+    }
+    nr_corr_batched_kernel<<<dim3(a.corr_blk[nbuf], B), 256, 0, s>>>(a, flat, sc, ss);
+    nr_finalize_batched_kernel<<<dim3(1, B), 1024, 0, s>>>(a, reg, means, sc, ss);
+    return launch_status("sg2_noise_reg_fwd_batched");
+}
+
+extern "C" int sg2_noise_reg_bwd_batched(float* gflat, const float* greg, const float* means, const float* flat,
+                                         const int64_t* table, int nbuf, int B, const void* scratch, int accumulate,
+                                         void* stream) {
+    NrArgs a;
+    if (nr_plan(a, "sg2_noise_reg_bwd_batched", table, nbuf, B) < 0) return -1;
+    SG2_CHECK(gflat && greg && means && flat && scratch,
+              "sg2_noise_reg_bwd_batched: gflat, greg, means, flat and scratch must be non-null");
+    SG2_CHECK(((uintptr_t)gflat % 16) == 0 && ((uintptr_t)flat % 16) == 0 && ((uintptr_t)scratch % 16) == 0 &&
+                  ((uintptr_t)means % 8) == 0,
+              "sg2_noise_reg_bwd_batched: gflat, flat and scratch must be 16-byte aligned, means 8-byte aligned");
+    nr_bwd_batched_kernel<<<dim3(a.bwd_blk[nbuf], B), 256, 0, as_stream(stream)>>>(
+        a, gflat, greg, means, flat, (const float*)scratch, nr_sample_stride(a), accumulate);
+    return launch_status("sg2_noise_reg_bwd_batched");
+}
+
+extern "C" int sg2_noise_normalize_batched(float* flat, const int64_t* table, int nbuf, int B, void* stream) {
+    NrArgs a;
+    if (nr_plan(a, "sg2_noise_normalize_batched", table, nbuf, B) < 0) return -1;
+    SG2_CHECK(flat, "sg2_noise_normalize_batched: flat must be non-null");
+    SG2_CHECK(((uintptr_t)flat % 16) == 0, "sg2_noise_normalize_batched: flat must be 16-byte aligned");
+    nr_normalize_batched_kernel<<<dim3(nbuf, B), 1024, 0, as_stream(stream)>>>(a, flat);
+    return launch_status("sg2_noise_normalize_batched");
 }

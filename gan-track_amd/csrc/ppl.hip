@@ -6,45 +6,15 @@
 //                          size, 7,995,392 floats per image for VGG16 at 256^2).
 // Both are HBM-bound: what counts is one pass and 16-byte accesses.
 //
-// sg2_lpips_pair_dist, the summation tree (it depends on F only -- not on B, the pair's row, or any address):
-//   element j belongs to chunk j / 8192, float4 group k = (j % 8192) / 1024, lane t = (j % 1024) / 4, component i = j % 4.
-//   stage 1 (one workgroup of 256 threads per (chunk, pair)):
-//     a thread keeps four accumulators, one per component i, each a SERIAL RUN of 8 squares (k = 0..7);
-//     the four are added as a tree of depth 2, then a wave butterfly (depth 6), then the four waves (depth 2);
-//   stage 2 (one workgroup of 256 threads per pair): thread t adds the chunk partials t, t + 256, ... in order --
-//     a SERIAL RUN of ceil(chunks / 256) terms, chunks = ceil(F / 8192) -- then butterfly (6) and four waves (2).
-//   Longest serial runs: 8, then ceil(ceil(F / 8192) / 256) (4 at F = 7,995,392); tree depth 2 + 6 + 2 + 6 + 2 = 18.
-//   (PPL_SERIAL / PPL_DEPTH below; torch_utils/ops/ppl.py pair_dist_tree(F) restates them for the tests' bound.)
-// No atomics; elements past F add +0.  Rows that are 16-byte aligned (feats aligned, F % 4 == 0) are read as float4,
-// any others element by element on the SAME tree, so the bits do not depend on the alignment either.
-#include "sg2_common.h"
+// sg2_lpips_pair_dist's summation tree (it depends on F only -- not on B, the pair's row, or any address) is
+// sqdist_tree.h's, shared with sg2_sqdist_rows_fwd: serial runs of 8, then ceil(ceil(F / 8192) / 256) (4 at
+// F = 7,995,392), tree depth 18 (PPL_SERIAL / PPL_DEPTH there; torch_utils/ops/ppl.py pair_dist_tree(F) restates them
+// for the tests' bound).  No atomics; elements past F add +0.  Rows that are 16-byte aligned (feats aligned,
+// F % 4 == 0) are read as float4, any others element by element on the SAME tree.
+#include "sqdist_tree.h"
 
 namespace sg2 {
 namespace {
-
-constexpr int PPL_THREADS = 256;
-constexpr int PPL_SERIAL = 8;                               // float4 groups of a thread per chunk
-constexpr int PPL_CHUNK = PPL_THREADS * 4 * PPL_SERIAL;     // 8192 elements
-constexpr int PPL_DEPTH = 2 + 6 + 2 + 6 + 2;
-
-__device__ __forceinline__ float ppl_wave_sum(float v) {    // a fixed butterfly: every lane gets the same bits
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// Sum over the workgroup's four waves, valid in every thread.  red: 4 floats of LDS.
-__device__ __forceinline__ float ppl_block_sum(float v, float* red) {
-    v = ppl_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[2]) + (red[1] + red[3]);
-}
-
-__device__ __forceinline__ float ppl_sq(float a, float b) {
-    const float d = __fsub_rn(a, b);
-    return __fmul_rn(d, d);
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(PPL_THREADS) void ppl_dist_partial_kernel(const float* __restrict__ feats, int64_t B,
@@ -52,49 +22,14 @@ __global__ __launch_bounds__(PPL_THREADS) void ppl_dist_partial_kernel(const flo
                                                                        float* __restrict__ part) {
     __shared__ float red[4];
     const int64_t b = blockIdx.y, c = blockIdx.x;
-    const float* r0 = feats + b * F;
-    const float* r1 = feats + (B + b) * F;
-    const int64_t j0 = c * PPL_CHUNK + (int64_t)threadIdx.x * 4;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    if (VEC) {      // F % 4 == 0: a float4 is inside the row or past its end as a whole
-        float4 a[PPL_SERIAL], d[PPL_SERIAL];
-#pragma unroll
-        for (int k = 0; k < PPL_SERIAL; ++k) {
-            const int64_t j = j0 + (int64_t)k * (PPL_THREADS * 4);
-            const bool in = j < F;
-            a[k] = in ? *(const float4*)(r0 + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-            d[k] = in ? *(const float4*)(r1 + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int k = 0; k < PPL_SERIAL; ++k) {
-            acc[0] = __fadd_rn(acc[0], ppl_sq(a[k].x, d[k].x));
-            acc[1] = __fadd_rn(acc[1], ppl_sq(a[k].y, d[k].y));
-            acc[2] = __fadd_rn(acc[2], ppl_sq(a[k].z, d[k].z));
-            acc[3] = __fadd_rn(acc[3], ppl_sq(a[k].w, d[k].w));
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < PPL_SERIAL; ++k) {
-            const int64_t j = j0 + (int64_t)k * (PPL_THREADS * 4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const bool in = j + i < F;
-                const float x = in ? r0[j + i] : 0.f, y = in ? r1[j + i] : 0.f;
-                acc[i] = __fadd_rn(acc[i], ppl_sq(x, y));
-            }
-        }
-    }
-    const float v = ppl_block_sum(__fadd_rn(__fadd_rn(acc[0], acc[2]), __fadd_rn(acc[1], acc[3])), red);
+    const float v = sqdist_chunk_sum<VEC>(feats + b * F, feats + (B + b) * F, F, c, red);
     if (threadIdx.x == 0) part[b * chunks + c] = v;
 }
 
 __global__ __launch_bounds__(PPL_THREADS) void ppl_dist_final_kernel(const float* __restrict__ part, int64_t chunks,
                                                                      float eps2, float* __restrict__ dist) {
     __shared__ float red[4];
-    const float* p = part + (int64_t)blockIdx.x * chunks;
-    float acc = 0.f;
-    for (int64_t i = threadIdx.x; i < chunks; i += PPL_THREADS) acc = __fadd_rn(acc, p[i]);
-    const float v = ppl_block_sum(acc, red);
+    const float v = sqdist_final_sum(part + (int64_t)blockIdx.x * chunks, chunks, red);
     if (threadIdx.x == 0) dist[blockIdx.x] = __fdiv_rn(v, eps2);
 }
 

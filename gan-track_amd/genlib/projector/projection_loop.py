@@ -15,7 +15,9 @@ Differences from the reference by design:
     those defaults;
   * projection_test passes num_steps and early_stopping from projector_kwargs (the reference's call omits the two
     required arguments and cannot run);
-  * projector_kwargs.class_name, when present, names the projector class to construct (default: this package's).
+  * projector_kwargs.class_name, when present, names the projector class to construct (default: this package's);
+  * projector_kwargs.batch > 1 projects `batch` slices at a time (_project_batched): the same slices from the same
+    starts, first all cold first slices, then all warm ones; at 1 (the default) the loop below runs as it always did.
 """
 import os
 import pickle
@@ -67,6 +69,10 @@ def projection_loop(run_dir='.', training_set_kwargs={}, projector_kwargs={}, ra
 
     first_num_steps = projector_kwargs.get('first_num_steps', FIRST_NUM_STEPS)
     first_early_stopping = projector_kwargs.get('first_early_stopping', FIRST_EARLY_STOPPING)
+    if int(projector_kwargs.get('batch', 1)) > 1:
+        projected_w = _project_batched(loader, projector, projector_kwargs, device, first_num_steps, first_early_stopping)
+        _dump(run_dir, projected_w)
+        return
     projected_w = util_general.nested_dict()
     current_patient, w_init = '', None
     for idx, (image, _label, fname) in enumerate(loader):
@@ -90,9 +96,80 @@ def projection_loop(run_dir='.', training_set_kwargs={}, projector_kwargs={}, ra
             current_patient = id_patient
             w_init = w_steps[best_step].detach().cpu()
         projected_w[id_patient][id_slice] = w_steps[best_step].detach().cpu().numpy()
+    _dump(run_dir, projected_w)
 
+
+def _dump(run_dir, projected_w):
     with open(os.path.join(run_dir, 'projected_w'), 'wb') as handle:
         pickle.dump(util_general.plain_dict(projected_w), handle, protocol=pickle.HIGHEST_PROTOCOL)
+
+
+def _selected(loader, step_patient_slice):
+    """The items the sequential loop projects, in dataset order: (group, first of its group, id_patient, id_slice,
+    image [1, modalities, H, W]).  A group is a run of consecutive selected items of one patient -- the sequential
+    loop's comparison with the previous selected item's patient."""
+    current_patient, group = '', -1
+    for idx, (image, _label, fname) in enumerate(loader):
+        if idx % step_patient_slice != 0:
+            continue
+        _, id_patient, id_slice = util_general.split_dos_path_into_components(path=fname[0])
+        id_slice = util_general.get_filename_without_extension(path=id_slice)[-5:]
+        first = id_patient != current_patient
+        if first:
+            current_patient, group = id_patient, group + 1
+        yield group, first, id_patient, id_slice, image
+
+
+def _project_batched(loader, projector, projector_kwargs, device, first_num_steps, first_early_stopping):
+    """projector_kwargs.batch > 1: the same slices from the same starts as the sequential loop, `batch` at a time
+    (projector.forward_batch).  Every warm slice starts from its own group's FIRST slice's best w, so all warm slices
+    are independent of one another, and so are all cold first slices:
+      phase A: the first slice of every group, cold (first_num_steps / first_early_stopping, not verbose), in dataset
+               order, `batch` at a time;
+      phase B: every other selected slice, warm from its group's first best w (a per-sample w_init), in dataset order,
+               `batch` at a time -- a batch may mix patients.
+    The last batch of a phase may be short.  The dataset is walked once per phase, so at most `batch` images are held.
+    Returns {patient: {slice: w}} with the keys in dataset order, as the sequential loop leaves them."""
+    batch = int(projector_kwargs.batch)
+    projected_w = util_general.nested_dict()
+    group_w = {}                # group -> its first slice's best w [num_ws, w_dim] (CPU)
+
+    def flush(pending, warm):
+        if not pending:
+            return
+        for _, id_patient, id_slice, _ in pending:
+            print(f'Patient:        {id_patient}')
+            print(f'Slice:          {id_slice}')
+        print('')
+        ids = [(id_patient, int(id_slice)) for _, id_patient, id_slice, _ in pending]
+        targets = torch.cat([image for _, _, _, image in pending]).to(device).to(torch.float32)
+        if warm:
+            w_steps, best_steps = projector.forward_batch(
+                ids=ids, targets=targets, num_steps=projector_kwargs.num_steps,
+                early_stopping=projector_kwargs.early_stopping, w_init=torch.stack([group_w[g] for g, _, _, _ in pending]),
+                verbose=projector_kwargs.verbose)
+        else:
+            w_steps, best_steps = projector.forward_batch(
+                ids=ids, targets=targets, num_steps=first_num_steps, early_stopping=first_early_stopping, verbose=False)
+        for b, (group, id_patient, id_slice, _) in enumerate(pending):
+            best = w_steps[b][int(best_steps[b])].detach().cpu()
+            if not warm:
+                group_w[group] = best
+            projected_w[id_patient][id_slice] = best.numpy()
+        pending.clear()
+
+    for warm in (False, True):
+        pending = []
+        for group, first, id_patient, id_slice, image in _selected(loader, projector_kwargs.step_patient_slice):
+            if not warm:
+                projected_w[id_patient][id_slice] = None        # the keys in dataset order
+            if first == warm:
+                continue
+            pending.append((group, id_patient, id_slice, image))
+            if len(pending) == batch:
+                flush(pending, warm)
+        flush(pending, warm)
+    return projected_w
 
 
 def projection_test(target_fname='.', run_dir='.', training_set_kwargs={}, projector_kwargs={}, random_seed=0,

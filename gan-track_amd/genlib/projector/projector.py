@@ -12,6 +12,11 @@ one flat float32 tensor (torch_utils/ops/noise_reg.py): the regulariser is 3 + 1
 sg2_adam_multi launch (training.optim.FlatAdam, torch.optim.Adam's arithmetic) and the renormalisation one launch,
 instead of several hundred tiny launches per step.
 
+forward_batch runs B such projections in one loop (the reference has no counterpart): all w and noise buffers of the
+batch in one buffer-major flat tensor (noise_reg.make_batched_table), one synthesis and one detector pass at batch B,
+per-sample loss sums (torch_utils/ops/proj_loss.py) and per-sample early stopping (optimise_batch).  forward is
+untouched by it.
+
 Differences from the reference by design:
   * the snapshot is read by this build's legacy.load_network_pkl (nothing embedded in the pickle is executed);
   * the LPIPS network is supplied offline (metrics.metric_utils: SG2_LPIPS_DETECTOR, else SG2_PR_DETECTOR, or
@@ -32,7 +37,7 @@ import torch.nn.functional as F
 import legacy
 from genlib.utils import util_general
 from metrics import metric_utils
-from torch_utils.ops import noise_reg
+from torch_utils.ops import noise_reg, proj_loss
 
 LPIPS_URL = 'https://nvlabs-fi-cdn.nvidia.com/stylegan2-ada-pytorch/pretrained/metrics/vgg16.pt'
 
@@ -79,6 +84,36 @@ def optimise(num_steps, early_stopping, step_fn):
                 print(f'\nEarly Stopping! Total steps: {step}')
                 break
     return best_step, best_loss
+
+
+def optimise_batch(num_steps, early_stopping, step_fn):
+    """`optimise` for B independent columns at once: step_fn(step) -> B losses.  Returns (best_steps, best_losses,
+    stop_steps), three lists of length B; per column the best step and loss are exactly what `optimise` returns on
+    that column's losses, and stop_step is the last step `optimise` would have run (num_steps - 1 if it never stops
+    early).  A stopped column keeps being computed while others run, but its later losses are discarded: its best is
+    frozen.  The loop ends when every column has stopped, so step_fn runs max(stop_steps) + 1 times."""
+    best_loss = best_step = stale = stop = None
+    for step in range(num_steps):
+        losses = [float(v) for v in step_fn(step)]
+        if best_loss is None:
+            B = len(losses)
+            best_loss, best_step, stale, stop = [np.inf] * B, [num_steps] * B, [0] * B, [num_steps - 1] * B
+            running = [True] * B
+        for b, loss in enumerate(losses):
+            if not running[b]:
+                continue
+            if loss < best_loss[b]:
+                best_step[b], best_loss[b], stale[b] = step, loss, 0
+            else:
+                stale[b] += 1
+                if stale[b] >= early_stopping:
+                    print(f'\nEarly Stopping! Sample {b}, total steps: {step}')
+                    running[b], stop[b] = False, step
+        if not any(running):
+            break
+    if best_loss is None:
+        return [], [], []
+    return best_step, best_loss, stop
 
 
 def w_statistics(G, w_avg_samples, device):
@@ -337,6 +372,217 @@ class StyleGAN2Projector(torch.nn.Module):
             self.logs(id_patient=id_patient, id_slice=id_slice, target=target, history=frame,
                       projected_w_steps=projected_w_steps)
         return projected_w_steps, best_step
+
+    def forward_batch(self, ids, targets, num_steps, early_stopping, w_init=None, verbose=False, verbose_logger=True):
+        """B independent projections in one optimisation loop.  ids: B (id_patient, id_slice) pairs; targets
+        [B, C, H, W] float32 in [0, 255]; w_init: None (cold: one w_avg and w_std for all), [num_ws, w_dim], or
+        [B, num_ws, w_dim] (per-sample mean, its own spread the scale, as forward's warm start) ->
+        (w of every step [B, num_steps, num_ws, w_dim], best_steps: B ints).
+
+        Samples share no variable: sample b's loss is  reg_b * regularize_noise_weight + sum_m (w_lpips dist[b, m] +
+        w_pix pix[b, m]),  the backward runs on the sum over b, and Adam is elementwise, so every sample is optimised as
+        forward() optimises it alone -- with one synthesis, one detector pass and a fixed number of small launches per
+        step whatever B is.  Early stopping is per sample (optimise_batch): a stopped sample is still computed while
+        others run, but its later steps are discarded (rows of the result left zero, as at batch 1).
+
+        Random draws: the initial noise per sample, then per buffer (torch.randn_like(noise_const), sample-major: at
+        B = 1 forward's sequence); then one torch.randn([B, 1, w_dim]) per step."""
+        def logprint(*args):
+            if verbose_logger:
+                print(*args)
+
+        G0 = self.G
+        B = len(ids)
+        if not 1 <= B <= noise_reg.MAX_BATCH:
+            raise RuntimeError(f'forward_batch: the batch must hold 1..{noise_reg.MAX_BATCH} projections; got {B}')
+        assert targets.detach().cpu().numpy().dtype == self.dtype
+        assert targets.min().item() >= 0.0
+        assert targets.max().item() <= 255.0
+        assert all(t.max().item() > 1.0 for t in targets)
+        assert targets.shape == (B, G0.img_channels, G0.img_resolution, G0.img_resolution)
+        since = time.time()
+        dev = self.device
+        targets = targets.to(dev).to(torch.float32).contiguous()
+        M = proj_loss.num_modalities(targets.shape[1])
+        modalities = self.modalities[:M]
+
+        G = copy.deepcopy(G0).eval().requires_grad_(False).to(dev)
+        num_ws = G.mapping.num_ws
+
+        if w_init is not None:      # warm start per sample: the mean is w_init[b]'s first row, its spread the scale
+            w_init = torch.as_tensor(w_init)
+            if w_init.ndim == 2:
+                w_init = w_init.unsqueeze(0).expand(B, -1, -1)
+            assert w_init.shape[0] == B
+            w_avgs, w_stds = [], []
+            for b in range(B):
+                w_avg = torch.unsqueeze(w_init[b], dim=0)[:, :1, :]
+                w_stds.append(torch.std(w_avg).item())
+                w_avgs.append(w_avg.detach().cpu().numpy())
+        else:
+            logprint(f'Computing W midpoint and stddev using {self.w_avg_samples} samples...')
+            w_avg, w_std = w_statistics(G, self.w_avg_samples, dev)
+            w_avgs, w_stds = [w_avg] * B, [w_std] * B
+
+        noise_names = [name for name, _ in G.synthesis.named_buffers() if 'noise_const' in name]
+        owners = [G.synthesis.get_submodule(name.rsplit('.', 1)[0]) if '.' in name else G.synthesis
+                  for name in noise_names]
+        detector = metric_utils.get_feature_detector(LPIPS_URL, device=dev)
+
+        def features(img):      # (the network normalises its input in place: hand it a copy)
+            return lpips_features(detector, img.clone())
+
+        with torch.no_grad():   # the target features [M B, F], row m B + b, once
+            t_rows = proj_loss.split_rows(targets)
+            if t_rows.shape[2] > 256:
+                t_rows = F.interpolate(t_rows, size=(256, 256), mode='area')
+            target_features = features(t_rows).to(torch.float32).contiguous()
+
+        w_first = torch.tensor(np.concatenate(w_avgs, axis=0), dtype=torch.float32, device=dev)     # [B, 1, C]
+        w_dim = w_first.shape[-1]
+        w_out = torch.zeros([B, num_steps, w_dim], dtype=torch.float32, device=dev)
+        noise_init = [[torch.randn_like(o._buffers['noise_const']) for o in owners] for _ in range(B)]
+        sizes = [tuple(n.shape) for n in noise_init[0]]
+        noise_init = [torch.stack([noise_init[b][k] for b in range(B)]).unsqueeze(1) for k in range(len(owners))]
+        table, total = noise_reg.make_batched_table(B, w_dim, [s[0] for s in sizes])
+        fused = fused_default() and torch.device(dev).type == 'cuda' and all(s[0] == s[1] for s in sizes) and \
+            noise_reg.supported(table)
+
+        if fused:
+            from training.optim import FlatAdam
+            wp = table[0][0] // B
+            flat = torch.zeros([total], dtype=torch.float32, device=dev)
+            flat[:B * wp].view(B, wp)[:, :w_dim] = w_first.view(B, w_dim)
+            for (off, r), n in zip(table, noise_init):
+                flat[off:off + B * r * r] = n.reshape(-1)
+            flat.requires_grad_(True)
+            optimizer = FlatAdam([flat], betas=(0.9, 0.999), lr=self.initial_learning_rate)
+        else:
+            w_opt = w_first.clone().requires_grad_(True)
+            noise_bufs = [n.clone().requires_grad_(True) for n in noise_init]       # [B, 1, R, R] leaves
+            for o, buf in zip(owners, noise_bufs):
+                o._buffers['noise_const'] = buf
+            optimizer = torch.optim.Adam([w_opt] + noise_bufs, betas=(0.9, 0.999), lr=self.initial_learning_rate)
+
+        histories = [util_general.list_dict() for _ in range(B)]
+        first_grads, schedules = [{} for _ in range(B)], []
+        print(f'Early stopping set to {early_stopping}')
+
+        def step_fn(step):
+            scheds = [self._schedule(step, num_steps, s) for s in w_stds]
+            lr, scales = scheds[0][0], [s[1] for s in scheds]       # (the learning rate does not depend on w_std)
+            for group in optimizer.param_groups:
+                group['lr'] = lr
+            if fused:
+                w, views = noise_reg.unflatten_batched(flat, table, B, w_dim)
+                for o, v in zip(owners, views):
+                    o._buffers['noise_const'] = v
+            else:
+                w, views = w_opt, noise_bufs
+
+            scale_t = torch.tensor([float(s) for s in scales], dtype=torch.float32).view(B, 1, 1).to(dev)
+            w_noise = torch.randn([B, 1, w_dim], device=dev) * scale_t
+            ws = (w + w_noise).repeat([1, num_ws, 1])
+            synth = G.synthesis(ws, noise_mode='const')
+            if fused:
+                det_in, pix = proj_loss.prep(synth, targets)                # [M B, 3, Hd, Hd], [B, M]
+                dist = proj_loss.sqdist_rows(features(det_in).to(torch.float32), target_features).view(M, B).t()
+                reg = noise_reg.noise_regularizer_batched(flat, table, B)   # [B]
+            else:
+                det_in, pix = proj_loss.prep_ref(synth, targets)
+                dist = proj_loss.sqdist_rows_ref(features(det_in), target_features).view(M, B).t()
+                reg = noise_reg.noise_regularizer_batched_ref(views)
+
+            loss = reg * self.regularize_noise_weight
+            cols = [reg.detach()]
+            for m in range(M):
+                d, p = self.w_lpips * dist[:, m], self.w_pix * pix[:, m]
+                loss = loss + d + p
+                cols += [d.detach(), p.detach()]
+            terms = torch.stack(cols + [loss.detach()], dim=1).tolist()     # [B, 2 M + 2]: one host read per step
+            for b in range(B):
+                histories[b]['reg_loss'].append(terms[b][0] * self.regularize_noise_weight)
+                for i, m in enumerate(modalities):
+                    histories[b][f'{m}_lpips_loss'].append(terms[b][1 + 2 * i])
+                    histories[b][f'{m}_pix_loss'].append(terms[b][2 + 2 * i])
+                histories[b]['tot_loss'].append(terms[b][-1])
+            schedules.append((lr, tuple(scales)))
+
+            if fused:
+                flat.grad = None
+                loss.sum().backward()
+                if step == 0:
+                    gw, gviews = noise_reg.unflatten_batched(flat.grad.detach(), table, B, w_dim)
+                    for b in range(B):
+                        first_grads[b]['w'] = gw[b].clone().view(1, 1, w_dim)
+                        first_grads[b]['noise'] = [v[b, 0].clone() for v in gviews]
+                optimizer.step_flat(flat.grad, [0], [0], write_grad=False)
+                w_out[:, step] = noise_reg.unflatten_batched(flat.detach(), table, B, w_dim)[0][:, 0]
+                noise_reg.normalize_noise_batched_(flat, table, B)
+            else:
+                optimizer.zero_grad(set_to_none=True)
+                loss.sum().backward()
+                if step == 0:
+                    for b in range(B):
+                        first_grads[b]['w'] = w_opt.grad[b].detach().clone().view(1, 1, w_dim)
+                        first_grads[b]['noise'] = [buf.grad[b, 0].detach().clone() for buf in noise_bufs]
+                optimizer.step()
+                w_out[:, step] = w_opt.detach()[:, 0]
+                noise_reg.normalize_noise_batched_ref_(noise_bufs)
+
+            losses = [t[-1] for t in terms]
+            logprint(f'step {step + 1:>4d}/{num_steps}, lr: {lr}: loss ' + ' '.join(f'{v:<5.2f}' for v in losses))
+            return losses
+
+        best_steps, best_losses, stop_steps = optimise_batch(num_steps, early_stopping, step_fn)
+
+        # a stopped sample's later steps are discarded: rows left zero and the history cut, as forward() leaves them
+        for b in range(B):
+            w_out[b, stop_steps[b] + 1:] = 0
+            histories[b] = {k: v[:stop_steps[b] + 1] for k, v in histories[b].items()}
+        with torch.no_grad():
+            if fused:
+                final = [flat.detach()[off:off + B * r * r].view(B, r, r).clone() for off, r in table]
+            else:
+                final = [buf.detach()[:, 0].clone() for buf in noise_bufs]
+        elapsed = time.time() - since
+        print('Optimization completed in {:.0f}m {:.0f}s'.format(elapsed // 60, elapsed % 60))
+        print('Best steps: ' + ' '.join(str(s) for s in best_steps))
+        print('Best losses: ' + ' '.join('{:4f}'.format(v) for v in best_losses))
+
+        projected_w_steps = w_out.unsqueeze(2).repeat([1, 1, num_ws, 1])        # [B, num_steps, num_ws, w_dim]
+        self.__dict__['last'] = dict(
+            batch=B, fused=fused, schedules=schedules,
+            samples=[dict(history=histories[b], first_grads=first_grads[b], best_loss=best_losses[b],
+                          best_step=best_steps[b], stop_step=stop_steps[b], w_avg=w_avgs[b], w_std=w_stds[b],
+                          noise=[n[b] for n in final]) for b in range(B)])
+
+        if self.save_final_projection:
+            projected_w = torch.stack([projected_w_steps[b, best_steps[b]] for b in range(B)])     # [B, num_ws, w_dim]
+            with torch.no_grad():       # (rendered with the generator's own noise, as the reference does): one synthesis
+                synth_images = (self.G.synthesis(projected_w, noise_mode='const') + 1) * (255 / 2)
+            import PIL.Image
+            for b, (id_patient, id_slice) in enumerate(ids):
+                id_slice = int(id_slice)
+                log_dir = os.path.join(self.outdir, id_patient, 'projections')
+                util_general.create_dir(log_dir)
+                np.savez(os.path.join(log_dir, f'w_{id_slice:05d}-best_step_{best_steps[b]}.npz'),
+                         w=projected_w[b].unsqueeze(0).cpu().numpy())
+                for idx_mode, mode in enumerate(self.modalities):
+                    log_dir = os.path.join(self.outdir, id_patient, mode, 'image_log')
+                    util_general.create_dir(log_dir)
+                    pair = np.concatenate([_to_uint8_hw(targets[b:b + 1], idx_mode),
+                                           _to_uint8_hw(synth_images[b:b + 1], idx_mode)], axis=1)
+                    PIL.Image.fromarray(pair.squeeze(-1)).save(
+                        os.path.join(log_dir, f'img_{id_slice:05d}-best_step_{best_steps[b]}.png'))
+
+        if verbose:
+            import pandas as pd
+            for b, (id_patient, id_slice) in enumerate(ids):
+                frame = pd.DataFrame.from_dict(dict(histories[b]), orient='index').transpose()
+                self.logs(id_patient=id_patient, id_slice=int(id_slice), target=targets[b:b + 1], history=frame,
+                          projected_w_steps=projected_w_steps[b])
+        return projected_w_steps, best_steps
 
     def logs(self, id_patient, id_slice, target, history, projected_w_steps):
         """The loss table and plots of one projection, and the video of its steps."""

@@ -26,7 +26,7 @@ REQUIRED = ('data', 'outdir', 'gpus', 'experiment', 'network_pkl')
 DEFAULTS = dict(modalities='MR_nonrigid_CT,MR_MR_T2', dataset='Pelvis_2.1', split='train', dtype='float32', desc=None,
                 seed=303, snap=50, workers=3, step_patient_slice=2, target_fname=None, num_steps=500, early_stopping=50,
                 w_lpips=1.0, w_pix=1e-4, save_final_projection=True, snap_video=60, snap_optimization_history=60,
-                verbose=False)
+                verbose=False, batch=1)
 
 
 def init_dataset_mi_multimodal_kwargs(data, dtype, split, modalities):
@@ -53,7 +53,7 @@ def build_config(**kwargs):
     c.image_snapshot_ticks = c.network_snapshot_ticks = opts.snap
     c.random_seed = c.training_set_kwargs.random_seed = opts.seed
     for k in ('experiment', 'network_pkl', 'step_patient_slice', 'target_fname', 'num_steps', 'early_stopping', 'w_lpips',
-              'w_pix', 'save_final_projection', 'snap_video', 'snap_optimization_history', 'verbose'):
+              'w_pix', 'save_final_projection', 'snap_video', 'snap_optimization_history', 'verbose', 'batch'):
         c.projector_kwargs[k] = opts[k]
     for k in ('first_num_steps', 'first_early_stopping'):      # this build's: the cold start's step count / patience
         if opts.get(k) is not None:
@@ -149,6 +149,8 @@ def launch_projection(c, desc, outdir, outdir_model):
               type=click.IntRange(min=1), default=None)
 @click.option('--first_early_stopping', help='Patience of a patient\'s first slice (this build; default 100000)',
               type=click.IntRange(min=1), default=None)
+@click.option('--batch', help='Projections optimised together per process (this build; 1: one at a time)',
+              metavar='INT', type=click.IntRange(min=1, max=64), default=1, show_default=True)
 def main(**kwargs):
     c, desc, outdir, outdir_model = build_config(**kwargs)
     launch_projection(c=c, desc=desc, outdir=outdir, outdir_model=outdir_model)

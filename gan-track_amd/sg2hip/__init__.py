@@ -93,6 +93,18 @@ SIGNATURES = {
     'sg2_noise_reg_fwd': [_vp, _vp, _vp, _c_i64p, _i, _vp, _vp],
     'sg2_noise_reg_bwd': [_vp, _vp, _vp, _vp, _c_i64p, _i, _vp, _i, _vp],
     'sg2_noise_normalize_multi': [_vp, _c_i64p, _i, _vp],
+    # (additive to ABI 11: the same step for B projections at once, the sample a grid dimension, csrc/noise_reg.hip)
+    'sg2_noise_reg_batched_scratch_bytes': [_c_i64p, _c_i64p, _i, _i],
+    'sg2_noise_reg_fwd_batched': [_vp, _vp, _vp, _c_i64p, _i, _i, _vp, _vp],
+    'sg2_noise_reg_bwd_batched': [_vp, _vp, _vp, _vp, _c_i64p, _i, _i, _vp, _i, _vp],
+    'sg2_noise_normalize_batched': [_vp, _c_i64p, _i, _i, _vp],
+    # (additive to ABI 11: the per-sample loss of a batched projection step, csrc/proj_loss.hip)
+    'sg2_proj_prep_scratch_bytes': [_c_i64p, _i, _i, _i],
+    'sg2_proj_prep_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i64, _vp],
+    'sg2_proj_prep_bwd': [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    'sg2_sqdist_rows_scratch_bytes': [_c_i64p, _i64, _i64],
+    'sg2_sqdist_rows_fwd': [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp],
+    'sg2_sqdist_rows_bwd': [_vp, _vp, _vp, _vp, _i64, _i64, _vp],
     # (additive to ABI 11: the perceptual-path-length passes, csrc/ppl.hip)
     'sg2_ppl_prep': [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     'sg2_lpips_pair_dist_scratch_bytes': [_c_i64p, _i64, _i64],

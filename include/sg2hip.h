@@ -440,6 +440,60 @@ int sg2_noise_reg_bwd(float* gflat, const float* greg, const float* means, const
                       int nbuf, const void* scratch, int accumulate, void* stream);
 int sg2_noise_normalize_multi(float* flat, const int64_t* table, int nbuf, void* stream);
 
+/* The same step for B independent projections at once (a batch of latents, each with its own noise buffers).
+ * ADDITIVE entry points: SG2_ABI_VERSION stays 11 -- the four calls above keep their kernels and results.
+ * Layout: buffer-major.  Row k of `table` is (off_k, R_k) as above, and the buffer holds B samples one after another:
+ * sample s of buffer k is the R_k x R_k block at flat + off_k + s R_k^2 (so [B, 1, R, R] views of flat are contiguous).
+ * 1 <= B <= 64, and off_k + B R_k^2 must stay below 2 GiB; nbuf, R, offsets and alignment as above; anything else is an
+ * argument error and no device work is issued.  The sample is a grid dimension, so the launch counts do not depend on B.
+ * Per sample the summation trees are those of the calls above: sample s's reg, means, gradient and normalised buffers
+ * are BITWISE what the batch-1 calls give on that sample's buffers alone.  No atomics; two calls give the same bits.
+ *
+ * sg2_noise_reg_batched_scratch_bytes: the scratch of the two calls below (B shares, each the batch-1 scratch rounded
+ *   up to 16 bytes).
+ * sg2_noise_reg_fwd_batched (3 launches): reg [B]; means [B][sum of levels][2], per sample as sg2_noise_reg_fwd's.
+ * sg2_noise_reg_bwd_batched (1 launch): gflat[off_k + s R_k^2 + i] (+)= greg[s] * d reg[s] / d flat[the same]; greg
+ *   device f32 [B]; `flat`, `means` and `scratch` as the forward call left them; accumulate != 0 adds, 0 assigns every
+ *   element of every sample of every buffer.  Nothing outside the buffers (the latents, padding) is read or written.
+ * sg2_noise_normalize_batched (1 launch): per sample and buffer, in place, x -= mean(x); x *= 1 / sqrt(mean(x^2)). */
+int sg2_noise_reg_batched_scratch_bytes(int64_t* bytes, const int64_t* table, int nbuf, int B);
+int sg2_noise_reg_fwd_batched(float* reg, float* means, const float* flat, const int64_t* table, int nbuf, int B,
+                              void* scratch, void* stream);
+int sg2_noise_reg_bwd_batched(float* gflat, const float* greg, const float* means, const float* flat,
+                              const int64_t* table, int nbuf, int B, const void* scratch, int accumulate, void* stream);
+int sg2_noise_normalize_batched(float* flat, const int64_t* table, int nbuf, int B, void* stream);
+
+/* The per-sample loss of a batched projection step (csrc/proj_loss.hip).  ADDITIVE entry points: SG2_ABI_VERSION stays
+ * 11.  All tensors f32, contiguous; no atomics, every sum a fixed tree: results are bitwise reproducible, and a sample
+ * (a row) gives the same bits alone or in a batch.
+ *
+ * sg2_proj_prep_fwd (2 launches): synth [B, C, H, H] (the generator's output) and target [B, C, H, H] in [0, 255], H a
+ *   power of two in 4..1024, 1 <= C <= 16, 16-byte aligned.  Channel rule (projector.split_modalities): C = 1: one
+ *   modality (M = 1), the channel repeated to three; C = 3: one RGB modality as it is; any other C: M = C modalities,
+ *   each channel repeated.  With s = (x + 1) * 127.5 (an add and a multiply, two roundings, never an FMA) it writes
+ *   det_in [M B, 3, Hd, Hd], row m B + b: s itself up to 256^2 (f = 1: bitwise the f32 torch composition
+ *   (synth + 1) * (255 / 2) and the split), above it the mean of s over f x f, f = H / 256, Hd = H / f;
+ *   pix [B][M] = mean (t - s)^2 over the modality's channels at full resolution (a repeated modality's three channels
+ *   are equal: the mean over its H H source elements).  The tree depends on C and H only (csrc/proj_loss.hip).
+ *   sg2_proj_prep_scratch_bytes: the scratch (one partial per 256 groups of 4 f^2 elements) the call needs.
+ * sg2_proj_prep_bwd (1 launch): assigns every element of gsynth [B, C, H, H] once:
+ *   127.5 (sum over the det_in channels that read (b, c) of gdet_in / f^2 + gpix[b][m] 2 (s - t) / n_m), n_m the
+ *   modality's source elements (H H, RGB: 3 H H).  gdet_in [M B, 3, Hd, Hd], gpix [B][M].
+ * sg2_sqdist_rows_fwd (2 launches): dist[r] = sum_j (f[r][j] - tf[r][j])^2 for R rows of any length F, f and tf
+ *   [R, F] row-contiguous behind two pointers (no concatenated copy), on sg2_lpips_pair_dist's tree, whose shape
+ *   depends on F only; rows that are not 16-byte aligned are read element by element on the same tree.
+ *   1 <= R <= 65535.  sg2_sqdist_rows_scratch_bytes: one partial per row and 8192-element chunk.
+ * sg2_sqdist_rows_bwd (1 launch): gf[r][j] = 2 g[r] (f[r][j] - tf[r][j]), every element assigned. */
+int sg2_proj_prep_scratch_bytes(int64_t* bytes, int B, int C, int H);
+int sg2_proj_prep_fwd(float* det_in, float* pix, const float* synth, const float* target, int B, int C, int H,
+                      void* scratch, int64_t scratch_bytes, void* stream);
+int sg2_proj_prep_bwd(float* gsynth, const float* gdet_in, const float* gpix, const float* synth, const float* target,
+                      int B, int C, int H, void* stream);
+int sg2_sqdist_rows_scratch_bytes(int64_t* bytes, int64_t R, int64_t F);
+int sg2_sqdist_rows_fwd(float* dist, const float* f, const float* tf, int64_t R, int64_t F, void* scratch,
+                        int64_t scratch_bytes, void* stream);
+int sg2_sqdist_rows_bwd(float* gf, const float* g, const float* f, const float* tf, int64_t R, int64_t F, void* stream);
+
 /* The two streaming passes of a perceptual-path-length sampler call (SG3/metrics/perceptual_path_length.py:71-89).
  * ADDITIVE entry points: SG2_ABI_VERSION stays 11 -- nothing that existed changes, and a caller built against the
  * ABI-11 header keeps working; callers that need them look the symbols up.
