@@ -500,3 +500,442 @@ def lb_judge_bound(got, ref, slack, dtype, what):
     elementwise outputs ('dc', 'out') are `dtype` values, the reductions f32."""
     return {k: assert_elementwise(v, ref[k], slack[k], dtype if k in ('dc', 'out') else torch.float32, f'{what} {k}')
             for k, v in got.items()}
+
+
+# ------------------------------------------------------------------ the f32 conv routes (test_conv_f32_gpu.py)
+# conv.hip runs an f32 convolution by default as a three-way bf16 split: x = h + m + l (split3 / split3x4: bf16
+# round-to-nearest-even residuals), and the GEMM takes six of the nine plane products in mfma_s3's order, in-loop
+# ('s3') or on planes sg2_split3 made once ('p3'); SG2_F32_EXACT=1 ('exact') takes the f32-input MFMA instead.
+S3_ORDER = ('lh', 'hl', 'mm', 'mh', 'hm', 'hh')     # (plane of the A operand, plane of the B operand), as mfma_s3
+S3_DROPPED = ('ml', 'lm', 'll')                      # never formed: below 2.02 2^-24 of a product together
+_PLANE = dict(h=0, m=1, l=2)
+CF_FORMS = ('s3', 'p3', 'exact')
+CF_WS_LIMIT = 1 << 23                                 # conv2d_gradfix._WS_LIMIT: split-K only below it
+CF_EXACT = dict(noise_gain=0.5, act=1, alpha=0.25, gain=2.0, clamp=64.0)      # the integer fixture's epilogue
+CF_RANDOM = dict(noise_gain=0.3, act=1, alpha=0.2, gain=2.0 ** 0.5, clamp=2.5)
+CF_WGRAD_ALPHA = dict(exact=0.25, random=0.7)
+SK_ITERS = 16                                         # conv1x1_smallk_dot: pixel passes per workgroup
+
+
+def cdiv(p, q):
+    return -(-p // q)
+
+
+def s3_split(x):
+    """(h, m, l) as f32 tensors: h = bf16(x), m = bf16(x - h), l = bf16((x - h) - m), every conversion
+    round-to-nearest-even and every residual an exact f32 subtraction: what split3 / split3x4 do.  h + m + l == x
+    for every normal f32 whose last bit is a normal bf16 value (|x| >= 2^-102)."""
+    x = x.float()
+    h = x.bfloat16().float()
+    r = x - h
+    m = r.bfloat16().float()
+    r = r - m
+    return h, m, r.bfloat16().float()
+
+
+def s3_products(xs, ws, drop=None):
+    """The plane products of mfma_s3 in its order (small terms first) as (name, A plane, B plane); `drop` leaves
+    one out: the mutant that gives the plane fixtures teeth."""
+    assert drop is None or drop in S3_ORDER, drop
+    return [(n, xs[_PLANE[n[0]]], ws[_PLANE[n[1]]]) for n in S3_ORDER if n != drop]
+
+
+def s3_matmul_emulated(X, W, drop=None, bk=32):
+    """X [M, K] @ W [K, N] as the split kernels form it: per `bk`-deep K stage the six products in order, each
+    one MFMA whose 32 bf16 products (exact in f32) are summed in float64 here and added to the f32 accumulator
+    with one rounding.  (How an MFMA rounds inside is not documented; on the plane fixtures nothing rounds.)"""
+    xs, ws = s3_split(X), s3_split(W)
+    acc = torch.zeros(X.shape[0], W.shape[1], dtype=torch.float32)
+    for k0 in range(0, X.shape[1], bk):
+        for _, a, b in s3_products([p[:, k0:k0 + bk] for p in xs], [p[k0:k0 + bk] for p in ws], drop):
+            acc = (acc.double() + a.double() @ b.double()).float()
+    return acc
+
+
+def cf_out_hw(k, stride, pad, transposed, H, W):
+    if transposed:
+        return (H - 1) * stride - 2 * pad + k, (W - 1) * stride - 2 * pad + k
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+def conv_fwd_plan(k, stride, pad, transposed, N, Cin, H, W, Cout, form='s3', workspace=True, dot=False):
+    """The host dispatch of sg2_conv2d_fused / launch_fwd for an f32 call, read from conv.hip (default
+    SG2_CONV_SPLIT_WGS = 512; 16-byte aligned operands).  `workspace`: whether the wrapper passes one (it does below
+    _WS_LIMIT output elements).  -> dict: family ('smallk', 'smallk_dot', 'generic'), OH, OW and, for the generic
+    implicit GEMM, BM, BN, BK, vec, nck, live_last (channels of the last K stage that are < Cin), phases [(M, ntaps,
+    nk)], splits, kper, grid, split_steps [phase][split] (K steps each split runs), empty [(phase, split)],
+    early_return [(phase, M tile)], dot_depth(det) (the longest chain of f32 additions of the dot reduction)."""
+    assert form in CF_FORMS
+    OH, OW = cf_out_hw(k, stride, pad, transposed, H, W)
+    P = OH * OW
+    plan = dict(OH=OH, OW=OW, K=k * k * Cin, splits=1)
+    if form != 'p3' and k == 1 and stride == 1 and pad == 0 and Cin <= 4 and Cout % 8 == 0 and 256 % (Cout // 8) == 0:
+        OG = Cout // 8
+        if dot:
+            ppi = 256 // OG
+            gx = cdiv(H * W, SK_ITERS * ppi)
+            plan.update(family='smallk_dot', grid=(gx, N), ppi=ppi, last_wg_pixels=H * W - (gx - 1) * SK_ITERS * ppi,
+                        dot_depth=lambda det: SK_ITERS + ppi + (det_sum_depth(gx, N * Cout) if det else gx + 1))
+        else:
+            plan.update(family='smallk', grid=(min(cdiv(N * H * W * OG, 256), 256 * 64),), items=N * H * W * OG)
+        return plan
+    # (conv1x1_smallo, the toRGB kernel, is 16-bit only: an f32 Cout <= 4 takes the implicit GEMM)
+    BK = 16 if form == 'exact' else 32
+    BM, BN = 128, 128 if Cout > 64 else 64
+    nck = cdiv(Cin, BK)
+    phases = []
+    if not transposed:
+        phases.append((N * OH * OW, k * k, k * k * nck))
+    else:
+        for py in range(stride):
+            for px in range(stride):
+                QH, QW = (OH - py + stride - 1) // stride, (OW - px + stride - 1) // stride
+                if QH <= 0 or QW <= 0:
+                    continue
+                nt = sum(1 for ky in range(k) if (py + pad - ky) % stride == 0) * \
+                    sum(1 for kx in range(k) if (px + pad - kx) % stride == 0)
+                phases.append((N * QH * QW, nt, nt * nck))
+    assert len(phases) <= 4, 'more than kMaxPhases: several launches (not modelled)'
+    blocks = sum(cdiv(M, 128) * cdiv(Cout, BN) for M, _, _ in phases)
+    maxnk = max([1] + [nk for _, _, nk in phases])
+    splits = 1
+    if blocks < 512 and workspace and N * P * Cout <= CF_WS_LIMIT:
+        splits = max(1, min(cdiv(512, blocks), maxnk // 4))
+    kper = cdiv(maxnk, splits)
+    maxM = max(M for M, _, _ in phases)
+    steps = [[max(0, min(nk, (s + 1) * kper) - s * kper) for s in range(splits)] for _, _, nk in phases]
+    plan.update(family='generic', BM=BM, BN=BN, BK=BK, vec=form == 'p3' or Cin % 4 == 0, nck=nck,
+                live_last=Cin - (nck - 1) * BK, phases=phases, splits=splits, kper=kper,
+                grid=(cdiv(maxM, BM), cdiv(Cout, BN), len(phases) * splits), split_steps=steps,
+                empty=[(p, s) for p in range(len(phases)) for s in range(splits) if steps[p][s] == 0],
+                early_return=[(p, t) for p, (M, _, _) in enumerate(phases) for t in range(cdiv(maxM, BM))
+                              if t * BM >= M],
+                dot_depth=lambda det: (det_sum_depth(P, Cout, N) if det else P) + 1)
+    return plan
+
+
+def conv_wgrad_plan(A, B, k, stride, pad, N, OH, OW, form='s3'):
+    """The host dispatch of conv2d_wgrad_impl / launch_wgrad for an f32 call (default SG2_CWGRAD_WGS = 1024; the
+    halo weight gradient is 16-bit only) -> dict: family ('smallb', 'smalla', 'generic'), K = N OH OW; generic: BM,
+    BN, BK, vec, tiles (mt, nt), chunks, splits, kper (pixels per split), split_pixels, grid; small forms: grid,
+    rows (deterministic slots), lanes (lanes a workgroup adds into one LDS cell).  depth(det, oikk): the additions
+    that follow a workgroup's own partial sum (atomics: one per split; det_sum / det_sum_oikk over the slots)."""
+    assert form in CF_FORMS
+    M = N * OH * OW
+    plan = dict(K=M)
+    one = k == 1 and stride == 1 and pad == 0
+    for fam, small, wide in (('smallb', B, A), ('smalla', A, B)):
+        if form != 'p3' and one and small <= 4 and wide % 8 == 0 and 256 % (wide // 8) == 0 and A * B <= 2048:
+            OG = wide // 8
+            g = min(cdiv(M * OG, 256), 1024)
+            rows = g * 256 // OG
+            plan.update(family=fam, grid=(g,), rows=rows, lanes=256 // OG, items=M * OG, splits=g,
+                        depth=lambda det, oikk=False: det_sum_depth(rows, A * B) if det else 256 // OG + g + 1)
+            return plan
+    BK = 16 if form == 'exact' else 32
+    BM, BN = 128 if A > 64 else 64, 128 if B > 64 else 64
+    mt, nt, KK = cdiv(A, BM), cdiv(B, BN), k * k
+    chunks = cdiv(M, BK)
+    splits = max(1, min(chunks // 8, cdiv(1024, mt * nt * KK)))
+    kper = cdiv(chunks, splits) * BK
+    splits = cdiv(M, kper)
+    nel = A * KK * B
+    plan.update(family='generic', BM=BM, BN=BN, BK=BK, vec=form == 'p3' or (A % 4 == 0 and B % 4 == 0),
+                tiles=(mt, nt), chunks=chunks, splits=splits, kper=kper, grid=(mt, nt, KK * splits),
+                split_pixels=[min(M, (s + 1) * kper) - s * kper for s in range(splits)],
+                depth=lambda det, oikk=False: (splits if oikk else det_sum_depth(splits, nel)) if det else splits + 1)
+    return plan
+
+
+# the case tables: the smallest shapes that reach each edge (test_conv_f32_host.py asserts that they do)
+CF_FWD_CASES = {        # name -> k, stride, pad, transposed, N, Cin, H, W, Cout
+    'f3': (3, 1, 1, False, 3, 40, 7, 7, 40),
+    'f3w': (3, 1, 1, False, 2, 8, 5, 6, 136),
+    'f1': (1, 1, 0, False, 3, 72, 7, 7, 24),
+    'f1d': (1, 1, 0, False, 2, 264, 4, 4, 72),
+    'fd': (3, 2, 0, False, 2, 16, 9, 9, 24),
+    'fu': (3, 2, 0, True, 4, 64, 5, 6, 24),
+    'f1t': (1, 1, 0, True, 2, 24, 6, 6, 40),
+    'fn': (3, 1, 1, False, 2, 13, 5, 5, 20),
+    'frgb1': (1, 1, 0, False, 2, 64, 6, 6, 1),
+    'frgb3': (1, 1, 0, False, 2, 64, 6, 6, 3),
+    'fk1_8': (1, 1, 0, False, 3, 1, 7, 7, 8),
+    'fk1_64': (1, 1, 0, False, 3, 1, 7, 7, 64),
+    'fk3_8': (1, 1, 0, False, 3, 3, 7, 7, 8),
+    'fk3_64': (1, 1, 0, False, 3, 3, 7, 7, 64),
+    'fk40': (1, 1, 0, False, 3, 3, 7, 7, 40),
+}
+CF_WGRAD_CASES = {      # name -> A, B, k, stride, pad, N, OH, OW
+    'w3': (40, 40, 3, 1, 1, 3, 7, 7),
+    'wA': (136, 8, 3, 1, 1, 2, 14, 20),
+    'wB': (8, 136, 3, 1, 1, 2, 14, 20),
+    'wAB': (72, 72, 3, 1, 1, 2, 6, 6),
+    'wd': (24, 16, 3, 2, 0, 2, 4, 4),
+    'w1': (24, 72, 1, 1, 0, 3, 7, 7),
+    'wn': (20, 13, 3, 1, 1, 2, 5, 5),
+    'wsb8_1': (8, 1, 1, 1, 0, 3, 7, 7),
+    'wsb64_1': (64, 1, 1, 1, 0, 3, 7, 7),
+    'wsb8_3': (8, 3, 1, 1, 0, 3, 7, 7),
+    'wsb64_3': (64, 3, 1, 1, 0, 3, 7, 7),
+    'wsa1_8': (1, 8, 1, 1, 0, 3, 7, 7),
+    'wsa1_64': (1, 64, 1, 1, 0, 3, 7, 7),
+    'wsa3_8': (3, 8, 1, 1, 0, 3, 7, 7),
+    'wsa3_64': (3, 64, 1, 1, 0, 3, 7, 7),
+}
+CF_PLANE_FWD, CF_PLANE_WGRAD = ('f1', 'f3'), ('w1', 'w3')
+CF_PLANE_FIXTURES = {'x24': ('lh', 'mh', 'hh'), 'w24': ('hl', 'hm', 'hh'), 'mm': ('mm', 'mh', 'hm', 'hh')}
+
+
+def cf_forms(cin_or_ab, wgrad_1x1_small=False):
+    """The arithmetic forms a case admits: 'p3' where conv2d_gradfix._p3 holds (every channel count % 8 == 0, and
+    for dw not the 1x1 small-depth kernels)."""
+    cs = cin_or_ab if isinstance(cin_or_ab, tuple) else (cin_or_ab,)
+    p3 = all(c % 8 == 0 for c in cs) and not wgrad_1x1_small
+    return ('s3', 'p3', 'exact') if p3 else ('s3', 'exact')
+
+
+def cf_wgrad_x_hw(k, stride, pad, OH, OW):
+    """The smallest input that gives an OH x OW gradient."""
+    return (OH - 1) * stride + k - 2 * pad, (OW - 1) * stride + k - 2 * pad
+
+
+def cf_pack(w, transposed):
+    """The packed weight [Cout][kh][kw][Cin] of w [Cout, Cin, kh, kw] (transposed: [Cin, Cout, kh, kw]) as a torch
+    permutation (conv2d_gradfix._pack_conv / _pack_convT without the pack kernel)."""
+    return (w.permute(1, 2, 3, 0) if transposed else w.permute(0, 2, 3, 1)).contiguous()
+
+
+def _cf_gen(name, *ints):
+    seed = sum((j + 1) * 7919 ** j * (int(v) + 3) for j, v in enumerate(ints))
+    return torch.Generator().manual_seed((seed + sum(map(ord, name)) * 104729) % (2 ** 31 - 1))
+
+
+def _ints(g, lo, hi, *s):
+    return torch.randint(lo, hi + 1, s, generator=g).double()
+
+
+def _pow2(g, lo, hi, *s):
+    return 2.0 ** _ints(g, lo, hi, *s)
+
+
+def _wshape(k, transposed, Cin, Cout):
+    return (Cin, Cout, k, k) if transposed else (Cout, Cin, k, k)
+
+
+def cf_fwd_operands(case, kind):
+    """Operands of a forward case as float64 (every value an f32 value).  kind 'exact': the integer fixture --
+    |x|, |w| <= 4, scales 2^-1..2^1, integer bias / noise / residual / dot_src (with CF_EXACT: noise_gain 0.5, alpha
+    0.25, gain 2, a clamp on the value grid) -- every product and partial sum is a multiple of 1/16 far below 2^24
+    quanta (cf_fwd_exact_refs asserts it), so all three arithmetic forms are exact in any order.  kind 'random': seeded
+    normals, w scaled by K^-1/2, scales in [0.5, 1.5)."""
+    k, stride, pad, tr, N, Cin, H, W, Cout = case
+    OH, OW = cf_out_hw(k, stride, pad, tr, H, W)
+    g = _cf_gen(kind, *[int(v) for v in case])
+    out = (N, Cout, OH, OW)
+    if kind == 'exact':
+        return dict(x=_ints(g, -4, 4, N, Cin, H, W), w=_ints(g, -4, 4, *_wshape(k, tr, Cin, Cout)),
+                    in_scale=_pow2(g, -1, 1, N, Cin), out_scale=_pow2(g, -1, 1, N, Cout),
+                    noise=_ints(g, -8, 8, N, 1, OH, OW), bias=_ints(g, -8, 8, Cout), residual=_ints(g, -8, 8, *out),
+                    dot_src=_ints(g, -4, 4, *out))
+
+    def rn(*s):
+        return torch.randn(*s, generator=g).float().double()
+    w = (torch.randn(*_wshape(k, tr, Cin, Cout), generator=g) / (k * k * Cin) ** 0.5).float().double()
+    return dict(x=rn(N, Cin, H, W), w=w,
+                in_scale=(torch.rand(N, Cin, generator=g) + 0.5).float().double(),
+                out_scale=(torch.rand(N, Cout, generator=g) + 0.5).float().double(),
+                noise=rn(N, 1, OH, OW), bias=rn(Cout), residual=rn(*out), dot_src=rn(*out))
+
+
+def _cf_conv(x, w, case):
+    k, stride, pad, tr = case[:4]
+    return (F.conv_transpose2d if tr else F.conv2d)(x, w, stride=stride, padding=pad)
+
+
+def conv_f32_slack(form, K, S, A):
+    """The absolute error an f32 conv route may carry in a sum of K products whose |.| sum is A (float64), reduced
+    over S further additions (split-K atomics or slots, det_sum's chain).
+    s3 / p3: (3 + 2 (6 K + S + 1)) 2^-24 A.  The 3: the three plane products that are never formed, m l' + l m' +
+    l l' with |m| <= 2^-8 |x| and |l| <= 2^-16 |x|: below 2.02 2^-24 per product.  6 K: one f32 addition per plane
+    product that is formed (the bf16 products themselves are exact in f32), S + 1 the additions after the
+    workgroup's own sum; the factor 2 is accumulation_slack's allowance for an MFMA accumulator that truncates.
+    exact: 2 (K + S + 1) 2^-24 A: one rounding per f32 product-and-add.
+    A modulated operand is rounded where the kernel rounds it (__fmul_rn in sstore and in split3_kernel) by the
+    reference itself, so it carries no slack."""
+    n = 3 + 2 * (6 * K + S + 1) if form in ('s3', 'p3') else 2 * (K + S + 1)
+    return n * EPS32 * A
+
+
+def cf_fwd_ref(case, op, form, S, dot_depth, epi=None, in_scale=False, out_scale=False, noise=False, bias=False,
+               residual=False, aux_mode=0, dot=False):
+    """sg2_conv2d_fused in float64 with its Judge 2 slack -> dict(c, A, y, aux, dot and slack_*).  c = conv(x *
+    in_scale, w) with the product rounded to f32 as the kernels stage it; v = clamp(lrelu(c out_scale + noise g +
+    bias) gain) through epilogue_slack; y = v + residual is one more f32 rounding; aux = c (mode 1) or v (mode 2);
+    dot[n, o] = sum_p c src: |src| slack_c plus one rounding of each product and `dot_depth` additions."""
+    x = op['x']
+    if in_scale:
+        x = (x.float() * op['in_scale'].float()[:, :, None, None]).double()
+    c, A = _cf_conv(x, op['w'], case), _cf_conv(x.abs(), op['w'].abs(), case)
+    sc = conv_f32_slack(form, case[0] * case[0] * case[5], S, A)
+    r = dict(c=c, A=A, slack_c=sc, y=c, slack_y=sc)
+    if epi is not None:
+        d = op['out_scale'][:, :, None, None] if out_scale else torch.ones(())
+        ng = op['noise'] * f32(epi['noise_gain']) if noise else torch.zeros(())
+        b = op['bias'][None, :, None, None] if bias else torch.zeros(())
+        al, gn, cl = f32(epi['alpha']) if epi['act'] == 1 else 1.0, f32(epi['gain']), f32(epi['clamp'])
+        v = c * d + ng + b
+        v = torch.where(v > 0, v, v * al) * gn
+        if cl >= 0:
+            v = v.clamp(-cl, cl)
+        sv = epilogue_slack(sc, c, d, ng, b, abs(gn), abs(al))
+        r.update(v=v, slack_v=sv, y=v, slack_y=sv)
+        if residual:
+            r['y'] = v + op['residual']
+            r['slack_y'] = sv + EPS32 * r['y'].abs()
+        if aux_mode:
+            r['aux'], r['slack_aux'] = (c, sc) if aux_mode == 1 else (v, sv)
+    if dot:
+        src = op['dot_src']
+        r['dot'] = (c * src).sum([2, 3])
+        r['A_dot'] = (A * src.abs()).sum([2, 3])
+        r['slack_dot'] = (sc * src.abs()).sum([2, 3]) + gamma(1 + dot_depth) * ((c.abs() + sc) * src.abs()).sum([2, 3])
+    return r
+
+
+def cf_assert_exact(sums, quantum=1.0 / 16):
+    """The precondition of Judge 1 on the reference alone (as lb_assert_exact): sums = [(name, A, values)], A the
+    float64 sum of |terms| -- below 2^24 quanta, so every partial sum in any order and in any of the three
+    arithmetic forms is an f32 value -- and `values` (the outputs) on the quantum's grid."""
+    for name, A, v in sums:
+        assert float(A.max()) / quantum < 2 ** 24, (name, float(A.max()))
+        assert torch.equal(v / quantum, (v / quantum).round()), f'{name}: a value off the {quantum} grid'
+        assert torch.equal(v.float().double(), v), name
+
+
+def cf_fwd_exact_refs(case):
+    """The integer fixture's references for a forward case: plain, the full epilogue with aux_mode 2, and (aux_mode
+    1) with the dot -- with the precondition asserted.  Every bound that matters is on a sum of |terms|: the conv
+    sum A (quantum 1/2), the epilogue value (|c d| + |noise g| + |b|) gain + |residual| (quantum 1/16) and the dot's
+    sum_p A |src|."""
+    op = cf_fwd_operands(case, 'exact')
+    full = dict(epi=CF_EXACT, in_scale=True, out_scale=True, noise=True, bias=True, residual=True)
+    refs = dict(plain=cf_fwd_ref(case, op, 's3', 1, 1), full=cf_fwd_ref(case, op, 's3', 1, 1, aux_mode=2, **full),
+                dot=cf_fwd_ref(case, op, 's3', 1, 1, aux_mode=1, dot=True, **full))     # (the slacks go unused)
+    for name, r in refs.items():
+        sums = [(f'{name} c', r['A'], r['c']), (f'{name} y', r['y'].abs(), r['y'])]
+        if 'v' in r:
+            mag = (r['A'] * op['out_scale'][:, :, None, None] + (op['noise'] * CF_EXACT['noise_gain']).abs() +
+                   op['bias'].abs()[None, :, None, None]) * CF_EXACT['gain'] + op['residual'].abs()
+            sums.append((f'{name} v', mag, r['v']))
+        if 'dot' in r:
+            sums.append((f'{name} dot', r['A_dot'], r['dot']))
+        cf_assert_exact(sums)
+    return op, refs
+
+
+def cf_wgrad_operands(case, kind):
+    """g [N, A, OH, OW], x [N, B, H, W], g_scale [N, A], x_scale [N, B] as float64; 'exact': integers |.| <= 4 and
+    scales 2^-1..2^1 (alpha 0.25: every term a multiple of 1/16), 'random': normals, scales in [0.5, 1.5)."""
+    A, B, k, stride, pad, N, OH, OW = case
+    H, W = cf_wgrad_x_hw(k, stride, pad, OH, OW)
+    g = _cf_gen('w' + kind, *case)
+    if kind == 'exact':
+        return dict(g=_ints(g, -4, 4, N, A, OH, OW), x=_ints(g, -4, 4, N, B, H, W), g_scale=_pow2(g, -1, 1, N, A),
+                    x_scale=_pow2(g, -1, 1, N, B))
+    return dict(g=torch.randn(N, A, OH, OW, generator=g).float().double(),
+                x=torch.randn(N, B, H, W, generator=g).float().double(),
+                g_scale=(torch.rand(N, A, generator=g) + 0.5).float().double(),
+                x_scale=(torch.rand(N, B, generator=g) + 0.5).float().double())
+
+
+def cf_wgrad_ref(case, op, form, S, scaled, alpha):
+    """sg2_conv2d_wgrad in float64 -> (dw [A, B, k, k], sum of |terms|, slack): both operands modulated with the
+    product rounded to f32 (as the kernels' sstore and split3_kernel), K = N OH OW products per element through
+    conv_f32_slack, and alpha applied to each workgroup's partial sum: one more f32 rounding of values whose |.|
+    sums to at most |alpha| A."""
+    A, B, k, stride, pad, N, OH, OW = case
+    g, x = op['g'], op['x']
+    if scaled:
+        g = (g.float() * op['g_scale'].float()[:, :, None, None]).double()
+        x = (x.float() * op['x_scale'].float()[:, :, None, None]).double()
+    al = f32(alpha)
+    kw = dict(stride=stride, padding=pad)
+    dw = torch.nn.grad.conv2d_weight(x, (A, B, k, k), g, **kw) * al
+    mag = torch.nn.grad.conv2d_weight(x.abs(), (A, B, k, k), g.abs(), **kw) * abs(al)
+    return dw, mag, conv_f32_slack(form, N * OH * OW, S, mag) + (EPS32 * mag if al != 1.0 else 0.0)
+
+
+def cf_wgrad_exact_refs(case):
+    """The integer fixture's dw references, with both scales and alpha and with none; the precondition asserted."""
+    op = cf_wgrad_operands(case, 'exact')
+    refs = {}
+    for name, scaled, alpha in (('scaled', True, CF_WGRAD_ALPHA['exact']), ('plain', False, 1.0)):
+        dw, mag, _ = cf_wgrad_ref(case, op, 's3', 1, scaled, alpha)
+        cf_assert_exact([(f'dw {name}', mag / min(alpha, 1.0), dw)])      # (the partial sums before alpha)
+        refs[name] = dw
+    return op, refs
+
+
+# ---- the plane fixtures: every output has at most one nonzero product and the float64 result is an f32 value, so
+# the six-product scheme is exact and every product class a fixture needs is load-bearing
+def cf_plane_values(kind, role, g, *s):
+    """role 'a' (the GEMM's A operand: x of a forward conv, g of a weight gradient) or 'b' (w; x of a dw)."""
+    n = 1
+    for v in s:
+        n *= v
+    sign = (torch.randint(0, 2, (n,), generator=g) * 2 - 1).double()
+    if kind == 'mm':        # 1 + q 2^-11, q odd <= 15: h + m with l = 0; a product is a multiple of 2^-22 below 2
+        v = 1 + (torch.randint(0, 8, (n,), generator=g) * 2 + 1).double() * 2.0 ** -11
+    elif (kind == 'x24') == (role == 'a'):      # 24 significant bits (the last one set), random sign
+        v = sign * ((torch.randint(0, 2 ** 22, (n,), generator=g) * 2 + 1).double() * 2.0 ** -23 + 1)
+    else:                   # +-2^k: one plane, so the partner's h, m and l each meet it once
+        v = sign * 2.0 ** torch.randint(-3, 4, (n,), generator=g).double()
+    return v.view(*s)
+
+
+def cf_plane_fwd_operands(case, kind, sparse):
+    """(x, w) of a plane fixture for a forward case (float64).  sparse 'a': x nonzero in one channel per pixel (1x1)
+    or on an every-third-pixel lattice, one channel per lattice point (3x3, stride 1), against a dense w; sparse
+    'b': w a one-hot (c, ky, kx) per output channel against a dense x."""
+    k, stride, pad, tr, N, Cin, H, W, Cout = case
+    assert stride == 1 and not tr and k in (1, 3)
+    g = _cf_gen(kind + sparse, *[int(v) for v in case])
+    x = cf_plane_values(kind, 'a', g, N, Cin, H, W)
+    w = cf_plane_values(kind, 'b', g, Cout, Cin, k, k)
+    if sparse == 'a':
+        keep = torch.zeros(N, Cin, H, W, dtype=torch.bool)
+        ch = torch.randint(0, Cin, (N, H, W), generator=g)
+        keep.scatter_(1, ch[:, None], True)
+        if k == 3:
+            lat = torch.zeros(H, W, dtype=torch.bool)
+            lat[1::3, 1::3] = True
+            keep &= lat
+        x = x * keep
+    else:
+        keep = torch.zeros(Cout, Cin * k * k, dtype=torch.bool)
+        keep.scatter_(1, torch.randint(0, Cin * k * k, (Cout, 1), generator=g), True)
+        w = w * keep.view(Cout, Cin, k, k)
+    return x, w
+
+
+def cf_plane_wgrad_operands(case, kind, sparse):
+    """(g, x) of a plane fixture for a weight-gradient case: the sparse operand ('a': g, 'b': x) is nonzero at one
+    pixel of one sample per channel, the other one dense."""
+    A, B, k, stride, pad, N, OH, OW = case
+    H, W = cf_wgrad_x_hw(k, stride, pad, OH, OW)
+    rng = _cf_gen('w' + kind + sparse, *case)
+    g = cf_plane_values(kind, 'a', rng, N, A, OH, OW)
+    x = cf_plane_values(kind, 'b', rng, N, B, H, W)
+    t, C, hw = (g, A, OH * OW) if sparse == 'a' else (x, B, H * W)
+    keep = torch.zeros(C, N * hw, dtype=torch.bool)
+    keep.scatter_(1, torch.randint(0, N * hw, (C, 1), generator=rng), True)
+    keep = keep.view(C, N, *t.shape[2:]).transpose(0, 1)
+    return (g * keep, x) if sparse == 'a' else (g, x * keep)
+
+
+def cf_plane_assert_one_term(terms, ref, what):
+    """terms: the number of nonzero products per output (the same operation on the operands' nonzero masks); ref:
+    the float64 result -- at most one product each, every result an f32 value, and a fair share of the outputs nonzero."""
+    assert float(terms.max()) <= 1, (what, float(terms.max()))
+    assert torch.equal(ref.float().double(), ref), what
+    assert float((ref != 0).double().mean()) > 0.05, what
