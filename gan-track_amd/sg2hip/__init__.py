@@ -117,6 +117,10 @@ SIGNATURES = {
     # (additive to ABI 11: the summed power spectrum of an image batch, a pruned DFT on the f64 MFMA, csrc/spectrum.hip)
     'sg2_power_spectrum_scratch_bytes': [_c_i64p, _i, _i, _i, _i],
     'sg2_power_spectrum_sum': [_vp, _vp, _i, _c_i64p, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    # (additive to ABI 11: SSIM and MSE of image pairs on f64 moments, one pass over both images, csrc/ssim.hip)
+    'sg2_ssim_scratch_bytes': [_c_i64p, _i, _i, _i, _i],
+    'sg2_ssim_mse': [_vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_double), ctypes.c_double, _vp, _i64,
+                     _vp],
 }
 ABI_VERSION = 11
 

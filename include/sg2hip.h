@@ -588,6 +588,28 @@ int sg2_power_spectrum_sum(double* out, const void* img, int dtype, const int64_
                            int interp, const double* window, const double* mean, const double* std,
                            const double* twiddle, void* scratch, int64_t scratch_bytes, void* stream);
 
+/* Structural similarity (Wang et al. 2004, the original formulation) and mean squared error of N C image pairs in one
+ * pass over the two images (csrc/ssim.hip).  ADDITIVE entry points: SG2_ABI_VERSION stays 11.
+ *
+ * x, y f32 [N, C, H, W] contiguous, DEVICE pointers; window11: HOST pointer to the 11 f64 weights g of the separable
+ * window w = g g^T (the Gaussian of sigma 1.5 normalised to sum 1 is the caller's to pass); data_range L > 0.
+ * Valid positions only, OH x OW = (H - 10) x (W - 10):
+ *   mx = sum w x, my = sum w y, sxx = sum w x^2 - mx^2, syy = sum w y^2 - my^2, sxy = sum w x y - mx my
+ *   ssim = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sxx + syy + C2)),  C1 = (0.01 L)^2, C2 = (0.03 L)^2
+ * out f64 [N C][2], WRITTEN: out[i][0] = mean of ssim over the valid positions, out[i][1] = mean of (x - y)^2 over all
+ * H W pixels.  map, when non-null: f32 [N C][OH][OW], every element written once, ssim rounded to f32.
+ * The five moments are f64 fma chains (horizontal, then vertical, taps in increasing order) and the expression is
+ * evaluated in f64 without contraction: x against itself gives exactly 1.0 everywhere.  No atomics: every 16 x 32 output
+ * tile writes its two partial sums to scratch [N C][tiles][2] and a finalize launch adds them in an order fixed by
+ * (H, W): two calls give the same bits, a pair gives the same bits alone or in a batch, and map == NULL does not change
+ * out.  Every scratch element the call reads it has written itself.  2 launches.
+ * N, C >= 1, H and W in 11..1024, data_range > 0; anything else, a null out, x, y, window11 or scratch, or a short
+ * scratch is an argument error and nothing is launched.
+ * sg2_ssim_scratch_bytes: 16 bytes per tile and pair, N C ceil(OH / 16) ceil(OW / 32) 16. */
+int sg2_ssim_scratch_bytes(int64_t* bytes, int N, int C, int H, int W);
+int sg2_ssim_mse(double* out, float* map, const float* x, const float* y, int N, int C, int H, int W,
+                 const double* window11, double data_range, void* scratch, int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
