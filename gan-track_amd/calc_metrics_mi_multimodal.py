@@ -130,12 +130,14 @@ def calc_metrics(**kwargs):
 
     \b
     Metrics:
-      fid50k_full  Frechet inception distance against the full dataset.
-      pr50k3_full  Precision and recall against the full dataset.
-      ppl2_wend    Perceptual path length in W, endpoints, full image.
-      fid50k       Frechet inception distance against 50k real images.
-      pr50k3       Precision and recall against 50k real images.
-      kid50k       Kernel inception distance against 50k real images.
+      fid50k_full    Frechet inception distance against the full dataset.
+      pr50k3_full    Precision and recall against the full dataset.
+      ppl2_wend      Perceptual path length in W, endpoints, full image.
+      fid50k         Frechet inception distance against 50k real images.
+      pr50k3         Precision and recall against 50k real images.
+      kid50k         Kernel inception distance against 50k real images.
+      prdc50k5_full  Precision, recall, density and coverage (k = 5) against the full dataset.
+      prdc50k5       Precision, recall, density and coverage (k = 5) against 50k real images.
     """
     args = build_args(**kwargs)
     if args.verbose:

@@ -37,6 +37,8 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // (512 instead of 768 slot rows per 256 x 256 x 32 products) with 4 instead of 6 DMA instructions per wave and step.
 constexpr int N_BM = 256, N_NS = 3;
 constexpr int N_MAXSPLITS = 64;
+// what the epilogue keeps: the k + 1 smallest d2 per row, one flag per row, or a count per row and a flag per column
+constexpr int M_RADII = 0, M_MEMBER = 1, M_COUNT = 2;
 template <int WN> struct Geo {
     static constexpr int BN = 64 * WN;                      // columns per tile
     static constexpr int NW = 2 * WN;                       // waves
@@ -45,9 +47,10 @@ template <int WN> struct Geo {
     static constexpr int ADMA = N_BM / 16 / NW;             // of which row-panel rows (4 / 2)
     static constexpr int SRC = 4 * WN;                      // (lane group, wave) pairs that share a row
     static constexpr size_t RING = (size_t)N_NS * SLOT;
-    static constexpr size_t lds(int kl, bool member) {      // the ring, reused by the end-of-kernel merge
-        const size_t merge = (size_t)N_BM * SRC * (member ? 1 : kl * sizeof(float));
-        return merge > RING ? merge : RING;
+    static constexpr size_t lds(int kl, int mode) {         // the ring, reused by the end-of-kernel merge
+        const size_t merge = (size_t)N_BM * SRC * (mode == M_MEMBER ? 1 : mode == M_COUNT ? sizeof(int) : kl * sizeof(float));
+        // (counting: 64 bytes behind the ring carry a tile's column flags from the lower to the upper row half)
+        return (merge > RING ? merge : RING) + (mode == M_COUNT ? 64 : 0);
     }
 };
 
@@ -73,16 +76,19 @@ struct KnnArgs {
     const void* cols;       // [ncols][d] fp16: the panel it walks (radii: x, membership: the manifold)
     const float* nrow;      // [rows_pad] squared norms
     const float* ncol;      // [>= col_tiles * 128] squared norms, +inf past ncols in the radii pass
-    const float* thr;       // membership: [>= col_tiles * 128] d2 thresholds, -inf past ncols
-    void* part;             // radii: float [splits][rows_pad][KL]; membership: uint32 [splits][rows_pad]
+    const float* thr;       // membership, counting: [>= col_tiles * 128] d2 thresholds, -inf past ncols
+    void* part;             // radii: float [splits][rows_pad][KL]; membership: uint32 [splits][rows_pad];
+                            // counting: int32 [splits][rows_pad]
+    uint8_t* colpart;       // counting: [row_tiles][cols_pad] column flags, one per (row tile, column)
     int nrows, ncols, d;
     int row_tiles, col_tiles, tiles_per_split, splits;
-    int64_t rows_pad;
+    int64_t rows_pad, cols_pad;
 };
 
-template <int KL, bool MEMBER, int WN>
+template <int KL, int MODE, int WN>
 __global__ __launch_bounds__(128 * WN, 4 / WN) void knn_gemm_kernel(KnnArgs a) {
     typedef Geo<WN> G;
+    constexpr bool MEMBER = MODE == M_MEMBER, COUNT = MODE == M_COUNT;
     constexpr int N_BN = G::BN, N_SLOT = G::SLOT, N_DMA = G::DMA, N_ADMA = G::ADMA, NW = G::NW, SRC = G::SRC;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -150,6 +156,9 @@ __global__ __launch_bounds__(128 * WN, 4 / WN) void knn_gemm_kernel(KnnArgs a) {
     for (int jp = 0; jp < 8; ++jp) nr[jp] = a.nrow[m0 + wm * 128 + jp * 16 + l16];
     float L[8][KL];                                             // radii: the running k + 1 smallest d2, ascending
     unsigned hit = 0;                                           // membership: bit jp
+    int cnt[8];                                                 // counting: columns within their radius, per row
+#pragma unroll
+    for (int jp = 0; jp < 8; ++jp) cnt[jp] = 0;
 #pragma unroll
     for (int jp = 0; jp < 8; ++jp)
 #pragma unroll
@@ -184,13 +193,15 @@ __global__ __launch_bounds__(128 * WN, 4 / WN) void knn_gemm_kernel(KnnArgs a) {
 #pragma unroll
         for (int jc = 0; jc < 4; ++jc) {
             nb[jc] = *(const float4*)(a.ncol + colb + jc * 16);
-            th[jc] = MEMBER ? *(const float4*)(a.thr + colb + jc * 16) : float4{0.f, 0.f, 0.f, 0.f};
+            th[jc] = MEMBER || COUNT ? *(const float4*)(a.thr + colb + jc * 16) : float4{0.f, 0.f, 0.f, 0.f};
         }
         // radii: rows and columns are the same points; the tile holds diagonal entries if the ranges overlap
-        const bool diag = !MEMBER && ct * N_BN < m0 + N_BM && ct * N_BN + N_BN > m0;
+        const bool diag = MODE == M_RADII && ct * N_BN < m0 + N_BM && ct * N_BN + N_BN > m0;
+        unsigned cmask = 0;                           // counting: bit 4 jc + r, the lane's 16 columns over its 8 rows
 #pragma unroll
         for (int jp = 0; jp < 8; ++jp) {
             const int row = m0 + wm * 128 + jp * 16 + l16;
+            unsigned rbits = 0;                       // counting: this row's 16 flags, bit 4 jc + r
 #pragma unroll
             for (int jc = 0; jc < 4; ++jc) {
                 const float nbv[4] = {nb[jc].x, nb[jc].y, nb[jc].z, nb[jc].w};
@@ -201,12 +212,36 @@ __global__ __launch_bounds__(128 * WN, 4 / WN) void knn_gemm_kernel(KnnArgs a) {
                     if (MEMBER) {
                         // (the clamp at 0 cannot change d2 <= thr: thr is >= 0 or -inf)
                         hit |= d2 <= thv[r] ? 1u << jp : 0u;
+                    } else if (COUNT) {
+                        // (a row past nrows has a NaN norm: d2 is NaN and the comparison false for every threshold)
+                        rbits |= d2 <= thv[r] ? 1u << (jc * 4 + r) : 0u;
                     } else {
                         if (diag && row == colb + jc * 16 + r) d2 = 0.f;
                         if (d2 < L[jp][KL - 1]) list_insert<KL>(L[jp], fmaxf(d2, 0.f));
                     }
                     acc[jc][jp][r] = 0.f;
                 }
+            }
+            if (COUNT) {
+                cnt[jp] += __builtin_popcount(rbits);
+                cmask |= rbits;
+            }
+        }
+        if (COUNT) {
+            // the 16 lanes of a wave and the 2 waves (wm) that hold the same 16 columns: OR over the lanes by a
+            // butterfly, over the waves through 2 bytes of LDS behind the ring.  Every wave of the workgroup ends
+            // its tiles at the same step, so all of them meet at this barrier; the step barrier of the next tile
+            // lies between this read and the next write.  Lane l16 < 4 of the upper wave then stores the four flags
+            // of column fragment jc = l16 as one word: one partial per (row tile, column).
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) cmask |= (unsigned)__shfl_xor((int)cmask, off, 64);
+            unsigned short* lc = (unsigned short*)(smem_raw + G::RING);
+            if (wm == 1 && l16 == 0) lc[wn * 4 + q] = (unsigned short)cmask;
+            __syncthreads();                          // (with its fences: these are plain LDS accesses, not DMA)
+            if (wm == 0 && l16 < 4) {
+                const unsigned nib = (cmask | lc[wn * 4 + q]) >> (l16 * 4);
+                const unsigned word = (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
+                *(unsigned*)(a.colpart + (int64_t)rt * a.cols_pad + colb + l16 * 16) = word;
             }
         }
         kk = 0;
@@ -227,6 +262,16 @@ __global__ __launch_bounds__(128 * WN, 4 / WN) void knn_gemm_kernel(KnnArgs a) {
 #pragma unroll
         for (int s = 0; s < SRC; s += 4) v |= *(const unsigned*)(lm + tid * SRC + s);
         ((unsigned*)a.part)[(int64_t)sp * a.rows_pad + m0 + tid] = v ? 1u : 0u;
+    } else if (COUNT) {
+        int* lm = (int*)smem_raw;                                 // [256][SRC]
+#pragma unroll
+        for (int jp = 0; jp < 8; ++jp) lm[(wm * 128 + jp * 16 + l16) * SRC + src] = cnt[jp];
+        __syncthreads();
+        if (tid >= N_BM) return;
+        int v = 0;
+#pragma unroll
+        for (int s = 0; s < SRC; ++s) v += lm[tid * SRC + s];
+        ((int*)a.part)[(int64_t)sp * a.rows_pad + m0 + tid] = v;
     } else {
         float* lm = (float*)smem_raw;                             // [256][SRC][KL]
 #pragma unroll
@@ -329,6 +374,24 @@ __global__ __launch_bounds__(256) void knn_merge_hit_kernel(uint8_t* hit, const 
     hit[i] = v ? 1 : 0;
 }
 
+// count[i] = the sum of row i's partials over the splits; covered[j] = the OR of column j's partials over the row tiles
+__global__ __launch_bounds__(256) void knn_merge_count_kernel(int32_t* count, uint8_t* covered, const int* part,
+                                                              const uint8_t* colpart, int64_t p, int64_t n,
+                                                              int64_t rows_pad, int64_t cols_pad, int splits,
+                                                              int row_tiles) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < p) {
+        int v = 0;
+        for (int s = 0; s < splits; ++s) v += part[(int64_t)s * rows_pad + i];
+        count[i] = v;
+    }
+    if (i < n) {
+        unsigned v = 0;
+        for (int t = 0; t < row_tiles; ++t) v |= colpart[(int64_t)t * cols_pad + i];
+        covered[i] = v ? 1 : 0;
+    }
+}
+
 // ---- host side ----
 int num_cus() {
     static const int cus = [] {
@@ -394,10 +457,10 @@ KnnPlan make_plan(int64_t rows, int64_t cols) {
 
 constexpr int64_t kMaxOperand = 0x7fffffffLL;       // 32-bit buffer offsets (sg2_common.h make_rsrc)
 
-template <int KL, bool MEMBER, int WN>
+template <int KL, int MODE, int WN>
 int launch_gemm_wn(const KnnArgs& a, hipStream_t s, const char* what) {
-    auto kern = knn_gemm_kernel<KL, MEMBER, WN>;
-    constexpr size_t lds = Geo<WN>::lds(KL, MEMBER);
+    auto kern = knn_gemm_kernel<KL, MODE, WN>;
+    constexpr size_t lds = Geo<WN>::lds(KL, MODE);
     static_assert(lds <= 160 * 1024, "LDS");
     static bool attr_set = false;   // benign race: idempotent attribute
     if (!attr_set) {
@@ -409,9 +472,9 @@ int launch_gemm_wn(const KnnArgs& a, hipStream_t s, const char* what) {
     return launch_status(what);
 }
 
-template <int KL, bool MEMBER>
+template <int KL, int MODE>
 int launch_gemm(const KnnArgs& a, bool wide, hipStream_t s, const char* what) {
-    return wide ? launch_gemm_wn<KL, MEMBER, 4>(a, s, what) : launch_gemm_wn<KL, MEMBER, 2>(a, s, what);
+    return wide ? launch_gemm_wn<KL, MODE, 4>(a, s, what) : launch_gemm_wn<KL, MODE, 2>(a, s, what);
 }
 
 int check_common(const char* what, int dtype, int d, const void* scratch) {
@@ -460,8 +523,8 @@ extern "C" int sg2_knn_radii(float* radii, const void* x, int dtype, int64_t n, 
     a.d = d;
     a.row_tiles = p.row_tiles; a.col_tiles = p.col_tiles; a.tiles_per_split = p.tiles_per_split; a.splits = p.splits;
     a.rows_pad = p.rows_pad;
-    if (int rc = kl == 4 ? launch_gemm<4, false>(a, p.wide, s, "sg2_knn_radii")
-                         : launch_gemm<8, false>(a, p.wide, s, "sg2_knn_radii"))
+    if (int rc = kl == 4 ? launch_gemm<4, M_RADII>(a, p.wide, s, "sg2_knn_radii")
+                         : launch_gemm<8, M_RADII>(a, p.wide, s, "sg2_knn_radii"))
         return rc;
     const unsigned mb = (unsigned)cdiv(n, 256);
     if (kl == 4) knn_merge_radii_kernel<4><<<mb, 256, 0, s>>>(radii, f + p.off_part, n, p.rows_pad, p.splits, k, round16);
@@ -502,8 +565,62 @@ extern "C" int sg2_manifold_member(uint8_t* hit, const void* probes, int64_t p_n
     a.d = d;
     a.row_tiles = p.row_tiles; a.col_tiles = p.col_tiles; a.tiles_per_split = p.tiles_per_split; a.splits = p.splits;
     a.rows_pad = p.rows_pad;
-    if (int rc = launch_gemm<1, true>(a, p.wide, s, "sg2_manifold_member")) return rc;
+    if (int rc = launch_gemm<1, M_MEMBER>(a, p.wide, s, "sg2_manifold_member")) return rc;
     knn_merge_hit_kernel<<<(unsigned)cdiv(p_n, 256), 256, 0, s>>>(hit, (const unsigned*)(f + p.off_part), p_n, p.rows_pad,
                                                                  p.splits);
     return launch_status("sg2_manifold_member (merge)");
+}
+
+// Counting (density / coverage, Naeem et al. 2020): the membership pass with a counting epilogue that also reduces along
+// the rows.  Scratch: the membership layout with one int per (split, row), then uint8 [row_tiles][cols_pad] column flags.
+extern "C" int sg2_manifold_count_scratch_bytes(int64_t* bytes, int64_t p_n, int64_t n) {
+    SG2_CHECK(bytes, "sg2_manifold_count_scratch_bytes: bytes must be non-null");
+    SG2_CHECK(p_n >= 1 && n >= 1, "sg2_manifold_count_scratch_bytes: p and n must be >= 1");
+    const KnnPlan p = make_plan(p_n, n);
+    *bytes = p.bytes(1) + (int64_t)p.row_tiles * p.cols_pad;
+    return 0;
+}
+
+extern "C" int sg2_manifold_count(int32_t* count, uint8_t* covered, const void* probes, int64_t p_n,
+                                  const void* manifold, int64_t n, const float* radii, int dtype, int d, int round16,
+                                  void* scratch, int64_t scratch_bytes, void* stream) {
+    SG2_CHECK(count && covered && probes && manifold && radii && scratch,
+              "sg2_manifold_count: count, covered, probes, manifold, radii and scratch must be non-null");
+    if (int rc = check_common("sg2_manifold_count", dtype, d, scratch)) return rc;
+    SG2_CHECK(p_n >= 1 && n >= 1, "sg2_manifold_count: p and n must be >= 1");
+    SG2_CHECK(p_n * (int64_t)d * 2 <= kMaxOperand && n * (int64_t)d * 2 <= kMaxOperand,
+              "sg2_manifold_count: probes and manifold must each be below 2 GiB (32-bit buffer offsets)");
+    SG2_CHECK(((uintptr_t)probes % 16) == 0 && ((uintptr_t)manifold % 16) == 0,
+              "sg2_manifold_count: probes and manifold must be 16-byte aligned");
+    const KnnPlan p = make_plan(p_n, n);
+    SG2_CHECK(scratch_bytes >= p.bytes(1) + (int64_t)p.row_tiles * p.cols_pad,
+              "sg2_manifold_count: scratch too small (sg2_manifold_count_scratch_bytes)");
+    hipStream_t s = as_stream(stream);
+    float* f = (float*)scratch;
+    // A probe row past p reads as zeros: with a norm of 0 its d2 would be |b|^2, inside the ball of any manifold row
+    // with |b|^2 <= thr, and would set that column's flag.  Its norm is NaN instead: d2 is NaN, `<=` false.
+    knn_norm_kernel<<<(unsigned)cdiv(p.rows_pad, 4), 256, 0, s>>>(f, (const f16_t*)probes, p_n, p.rows_pad, d,
+                                                                 __builtin_nanf(""));
+    knn_norm_kernel<<<(unsigned)cdiv(p.cols_pad, 4), 256, 0, s>>>(f + p.off_ncol, (const f16_t*)manifold, n, p.cols_pad,
+                                                                 d, 0.f);
+    knn_thr_kernel<<<(unsigned)cdiv(p.cols_pad, 256), 256, 0, s>>>(f + p.off_thr, radii, n, p.cols_pad, round16);
+    if (int rc = launch_status("sg2_manifold_count (norms)")) return rc;
+    KnnArgs a{};
+    a.rows = probes;
+    a.cols = manifold;
+    a.nrow = f;
+    a.ncol = f + p.off_ncol;
+    a.thr = f + p.off_thr;
+    a.part = f + p.off_part;
+    a.colpart = (uint8_t*)(f + p.off_part + (int64_t)p.splits * p.rows_pad);
+    a.nrows = (int)p_n;
+    a.ncols = (int)n;
+    a.d = d;
+    a.row_tiles = p.row_tiles; a.col_tiles = p.col_tiles; a.tiles_per_split = p.tiles_per_split; a.splits = p.splits;
+    a.rows_pad = p.rows_pad;
+    a.cols_pad = p.cols_pad;
+    if (int rc = launch_gemm<1, M_COUNT>(a, p.wide, s, "sg2_manifold_count")) return rc;
+    knn_merge_count_kernel<<<(unsigned)cdiv(std::max(p_n, n), 256), 256, 0, s>>>(
+        count, covered, (const int*)a.part, a.colpart, p_n, n, p.rows_pad, p.cols_pad, p.splits, p.row_tiles);
+    return launch_status("sg2_manifold_count (merge)");
 }

@@ -4,7 +4,8 @@ report_metric) and its output contract (one JSON line per evaluation appended to
 <run_dir>/metric-<modality>-<metric>.jsonl); the FID metrics are the two the Claro / Pelvis runs name, the
 precision / recall metrics (pr50k3_full, pr50k3) the one further metric the reference adapted to its per-modality
 evaluation, and ppl2_wend the perceptual path length and kid50k the kernel inception distance its offline
-evaluation (calc_metrics_mi_multimodal.py) names."""
+evaluation (calc_metrics_mi_multimodal.py) names.  prdc50k5_full and prdc50k5 (precision, recall, density and
+coverage, Naeem et al. 2020) are this project's own: the reference has no such metric."""
 import json
 import os
 import time
@@ -17,6 +18,7 @@ from . import frechet_inception_distance
 from . import precision_recall
 from . import perceptual_path_length
 from . import kernel_inception_distance
+from . import density_coverage
 
 
 class _Registry:
@@ -139,3 +141,22 @@ def kid50k(opts):
     kid = kernel_inception_distance.compute_kid(opts, max_real=50000, num_gen=50000, num_subsets=100,
                                                 max_subset_size=1000)
     return dict(kid50k=kid)
+
+
+def _prdc(opts, name, max_real):
+    results = density_coverage.compute_prdc(opts, max_real=max_real, num_gen=50000, nhood_size=5)
+    return {f'{name}_{key}': results[key] for key in ('precision', 'recall', 'density', 'coverage')}
+
+
+@register_metric
+def prdc50k5_full(opts):
+    """Precision, recall, density and coverage, k = 5 (the paper's), against up to 200k real images."""
+    opts.dataset_kwargs.update(max_size=None, xflip=False)
+    return _prdc(opts, 'prdc50k5_full', 200000)
+
+
+@register_metric
+def prdc50k5(opts):
+    """The same against 50k real images."""
+    opts.dataset_kwargs.update(max_size=None)
+    return _prdc(opts, 'prdc50k5', 50000)

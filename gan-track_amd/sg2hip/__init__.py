@@ -89,6 +89,9 @@ SIGNATURES = {
     'sg2_knn_scratch_bytes': [_c_i64p, _i64, _i64, _i],
     'sg2_knn_radii': [_vp, _vp, _i, _i64, _i, _i, _i, _vp, _i64, _vp],
     'sg2_manifold_member': [_vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp],
+    # (additive to ABI 11: the membership pass with a counting epilogue -- density / coverage, csrc/knn.hip)
+    'sg2_manifold_count_scratch_bytes': [_c_i64p, _i64, _i64],
+    'sg2_manifold_count': [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i64, _vp],
     'sg2_noise_reg_scratch_bytes': [_c_i64p, _c_i64p, _i],
     'sg2_noise_reg_fwd': [_vp, _vp, _vp, _c_i64p, _i, _vp, _vp],
     'sg2_noise_reg_bwd': [_vp, _vp, _vp, _vp, _c_i64p, _i, _vp, _i, _vp],

@@ -61,3 +61,30 @@ def manifold_member(probes, manifold, radii, round16=True):
                                                   scratch.numel() * 4, _hip.stream_ptr(probes.device)),
                    'sg2_manifold_member')
     return hit.bool()
+
+
+def manifold_count(probes, manifold, radii, round16=True):
+    """(count int32 [p], covered bool [n]) of one pass over the p x n distances (HIP kernel sg2_manifold_count):
+    count[i] = the number of manifold rows j with dist(probe_i, manifold_j) <= radii[j], covered[j] = whether any probe
+    lies within radii[j] of manifold row j.  The balls, the distances and the `<=` are manifold_member's, so
+    `count > 0` equals manifold_member(...) bit for bit; density = count.sum() / (k p), coverage = covered.mean()
+    (Naeem et al. 2020).  probes [p, d], manifold [n, d], radii [n] (knn_radii of the manifold)."""
+    _hip.require_device(probes, manifold, radii)
+    probes, manifold = _features(probes, 'probes'), _features(manifold, 'manifold')
+    radii = radii.detach().to(torch.float32).contiguous()
+    (p, d), n = probes.shape, manifold.shape[0]
+    if manifold.shape[1] != d or radii.shape != (n,) or not (manifold.device == radii.device == probes.device):
+        raise RuntimeError(f'manifold_count: probes {list(probes.shape)}, manifold {list(manifold.shape)} and radii '
+                           f'{list(radii.shape)} do not fit together (one device, one d, one radius per manifold row)')
+    with torch.cuda.device(probes.device):
+        count = torch.empty([p], dtype=torch.int32, device=probes.device)
+        covered = torch.empty([n], dtype=torch.uint8, device=probes.device)
+        nbytes = ctypes.c_int64(0)
+        _hip.check(_hip.lib().sg2_manifold_count_scratch_bytes(ctypes.byref(nbytes), p, n),
+                   'sg2_manifold_count_scratch_bytes')
+        scratch = torch.empty([(nbytes.value + 3) // 4], dtype=torch.float32, device=probes.device)
+        _hip.check(_hip.lib().sg2_manifold_count(_hip.ptr(count), _hip.ptr(covered), _hip.ptr(probes), p,
+                                                 _hip.ptr(manifold), n, _hip.ptr(radii), _hip.F16, d,
+                                                 int(bool(round16)), _hip.ptr(scratch), scratch.numel() * 4,
+                                                 _hip.stream_ptr(probes.device)), 'sg2_manifold_count')
+    return count, covered.bool()

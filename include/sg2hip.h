@@ -418,6 +418,19 @@ int sg2_manifold_member(uint8_t* hit, const void* probes, int64_t p, const void*
                         const float* radii, int dtype, int d, int round16, void* scratch, int64_t scratch_bytes,
                         void* stream);
 
+/* Density and coverage (Naeem et al., ICML 2020) on the membership pass (additive to ABI 11): the same GEMM, tiles,
+ * distances, round16 and per-column `<=` thresholds as sg2_manifold_member, with an epilogue that counts instead of
+ * OR-ing and also reduces along the manifold axis.  One pass over the p x n distance tiles gives
+ *   count[i]   = #{ j < n : dist(probes_i, manifold_j) <= radii[j] }      (int32 [p]; density = sum / (k p))
+ *   covered[j] = 1 if dist(probes_i, manifold_j) <= radii[j] for any i < p, else 0      (uint8 [n]; coverage = mean)
+ * and count[i] > 0 is sg2_manifold_member's hit[i], bit for bit.  Integer sums and ORs of per-(split, row) and
+ * per-(row tile, column) partials, every partial written by the call that reads it: no atomics, no memset, bitwise
+ * reproducible.  The same argument rules as sg2_manifold_member; the scratch size is a query of its own. */
+int sg2_manifold_count_scratch_bytes(int64_t* bytes, int64_t p, int64_t n);
+int sg2_manifold_count(int32_t* count, uint8_t* covered, const void* probes, int64_t p, const void* manifold,
+                       int64_t n, const float* radii, int dtype, int d, int round16, void* scratch,
+                       int64_t scratch_bytes, void* stream);
+
 /* The small-tensor part of a latent projection step (ABI 11; SG3/genlib/projector/projector.py:259-268 the noise
  * regulariser, :294-298 the per-buffer renormalisation).  All noise buffers of a generator live in ONE flat f32 device
  * buffer; `table` is a HOST array int64 [nbuf][2] of (offset of the buffer in flat, in floats; R) rows, 1 <= nbuf <= 32.
