@@ -172,12 +172,12 @@ extern "C" int sg2_bias_act(void* y, const void* x, const void* b, const void* x
                             int dtype, int64_t numel, int64_t size_b, int64_t step_b, int grad, int act,
                             float alpha, float gain, float clamp, void* stream) {
     using namespace sg2;
-    SG2_CHECK(y != nullptr && x != nullptr, "sg2_bias_act: x and y must be non-null");
     SG2_CHECK(numel >= 0 && numel <= INT32_MAX, "sg2_bias_act: x is too large");
     SG2_CHECK(grad >= 0 && grad <= 2, "sg2_bias_act: grad must be 0, 1 or 2");
     SG2_CHECK(b == nullptr || (size_b > 0 && step_b > 0), "sg2_bias_act: bad bias geometry");
     SG2_CHECK(act >= 1 && act <= 9, "sg2_bias_act: unknown activation id");
-    if (numel == 0) return 0;
+    if (numel == 0) return 0;       // an empty tensor has no storage: its pointers are null and nothing is read
+    SG2_CHECK(y != nullptr && x != nullptr, "sg2_bias_act: x and y must be non-null");
     BAParams p{y, x, b, xref, yref, dy, (uint32_t)numel, (uint32_t)(b ? size_b : 1), (uint32_t)(b ? step_b : 1),
                alpha, gain, clamp};
     hipStream_t s = as_stream(stream);

@@ -72,6 +72,7 @@ const char* sg2_last_error(void);
  *   grad = 1: y = x * act'(...) * gain masked by |yref| < clamp     (x holds dL/dy)
  *   grad = 2: second-order term (needs dy, the first-order incoming gradient)
  * b / xref / yref / dy may be NULL (absent, like the reference's empty tensor).
+ * numel == 0 is a no-op whatever the pointers are (an empty tensor has no storage).
  * act: 1 linear, 2 relu, 3 lrelu, 4 tanh, 5 sigmoid, 6 elu, 7 selu, 8 softplus, 9 swish
  * (the reference's cuda_idx, bias_act.py:21-31).  clamp < 0 disables clamping. */
 int sg2_bias_act(void* y, const void* x, const void* b, const void* xref, const void* yref, const void* dy,
