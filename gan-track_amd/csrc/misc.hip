@@ -11,10 +11,10 @@ namespace {
 // Demodulation with the per-(o, i) weight energy kept for the backward: wsq[o,i] = sum_k w^2 (written when
 // wsq_out != null), d[n,o] = rsqrt(sum_i s[n,i]^2 wsq[o,i] + eps).  One workgroup per o; after wsq is in
 // LDS, eight lanes per sample reduce a row of s each (32 samples per pass, no block barrier per sample).
-__global__ __launch_bounds__(256) void demod_fwd_kernel(float* d, float* wsq_out, const float* s, const float* w,
-                                                        int N, int O, int I, int KK, float eps) {
-    __shared__ float wsq[1024];
-    const int o = blockIdx.x;
+// (the bodies are device functions over the workgroup's index and LDS: the single-layer kernels and the style
+// table's jobs, style_table_kernel below, run the same code and so give the same bits)
+__device__ __forceinline__ void demod_fwd_body(float* wsq, int o, float* d, float* wsq_out, const float* s,
+                                               const float* w, int N, int O, int I, int KK, float eps) {
     for (int i = threadIdx.x; i < I; i += 256) {
         const float* wr = w + ((int64_t)o * I + i) * KK;
         float acc = 0.f;
@@ -43,14 +43,20 @@ __global__ __launch_bounds__(256) void demod_fwd_kernel(float* d, float* wsq_out
         if (seg == 0 && n < N) d[(int64_t)n * O + o] = rsqrtf(acc + eps);
     }
 }
+__global__ __launch_bounds__(256) void demod_fwd_kernel(float* d, float* wsq_out, const float* s, const float* w,
+                                                        int N, int O, int I, int KK, float eps) {
+    __shared__ float wsq[1024];
+    demod_fwd_body(wsq, blockIdx.x, d, wsq_out, s, w, N, O, I, KK, eps);
+}
 
 // Backward of demod_fwd: with gu[n,o] = -1/2 dd[n,o] d[n,o]^3,
 //   gw[o,i,k] = 2 w[o,i,k] sum_n gu[n,o] s[n,i]^2     (workgroup per o)
 //   gs[n,i]   = 2 s[n,i]   sum_o gu[n,o] wsq[o,i]      (workgroup per (n, 64 i); four o-quarters reduced in LDS)
-__global__ __launch_bounds__(256) void demod_bwd_w_kernel(float* gw, const float* dd, const float* d, const float* s,
-                                                          const float* w, int N, int O, int I, int KK) {
-    __shared__ float gu[1024];
-    const int o = blockIdx.x;
+// add (optional, the table's jobs): a gradient the result is added to, element (o, i, k) at o ao + i ai + k ak -- the
+// two-term sum autograd makes of a tensor's two gradients, the product kept out of an fma as a separate add has it.
+__device__ __forceinline__ void demod_bwd_w_body(float* gu, int o, float* gw, const float* dd, const float* d,
+                                                 const float* s, const float* w, int N, int O, int I, int KK,
+                                                 const float* add, int ao, int ai, int ak) {
     for (int n = threadIdx.x; n < N; n += 256) {
         const float dv = d[(int64_t)n * O + o];
         gu[n] = -0.5f * dd[(int64_t)n * O + o] * dv * dv * dv;
@@ -64,15 +70,30 @@ __global__ __launch_bounds__(256) void demod_bwd_w_kernel(float* gw, const float
         }
         const float* wr = w + ((int64_t)o * I + i) * KK;
         float* gr = gw + ((int64_t)o * I + i) * KK;
-        for (int k = 0; k < KK; ++k) gr[k] = 2.f * wr[k] * acc;
+        if (!add) {
+            for (int k = 0; k < KK; ++k) gr[k] = 2.f * wr[k] * acc;
+        } else {
+            const float* ar = add + (int64_t)o * ao + (int64_t)i * ai;
+            for (int k = 0; k < KK; ++k) {
+                float v = 2.f * wr[k] * acc;
+                asm volatile("" : "+v"(v));
+                gr[k] = ar[(int64_t)k * ak] + v;
+            }
+        }
     }
 }
-
-__global__ __launch_bounds__(256) void demod_bwd_s_kernel(float* gs, const float* dd, const float* d, const float* s,
-                                                          const float* wsq, int N, int O, int I) {
+__global__ __launch_bounds__(256) void demod_bwd_w_kernel(float* gw, const float* dd, const float* d, const float* s,
+                                                          const float* w, int N, int O, int I, int KK) {
     __shared__ float gu[1024];
-    __shared__ float part[4][64];
-    const int n = blockIdx.x, i = blockIdx.y * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
+    demod_bwd_w_body(gu, blockIdx.x, gw, dd, d, s, w, N, O, I, KK, nullptr, 0, 0, 0);
+}
+
+// (lds: 1024 floats of gu, then the 4 x 64 partials; add: as demod_bwd_w_body's, contiguous [N, I])
+__device__ __forceinline__ void demod_bwd_s_body(float* gu, int n, int by, float* gs, const float* dd, const float* d,
+                                                 const float* s, const float* wsq, int N, int O, int I,
+                                                 const float* add) {
+    float (*part)[64] = reinterpret_cast<float (*)[64]>(gu + 1024);
+    const int i = by * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
     for (int o = threadIdx.x; o < O; o += 256) {
         const float dv = d[(int64_t)n * O + o];
         gu[o] = -0.5f * dd[(int64_t)n * O + o] * dv * dv * dv;
@@ -92,9 +113,20 @@ __global__ __launch_bounds__(256) void demod_bwd_s_kernel(float* gs, const float
     }
     part[q][threadIdx.x & 63] = acc;
     __syncthreads();
-    if (q == 0 && i < I)
-        gs[(int64_t)n * I + i] = 2.f * s[(int64_t)n * I + i] * (part[0][threadIdx.x] + part[1][threadIdx.x] +
-                                                                 part[2][threadIdx.x] + part[3][threadIdx.x]);
+    if (q == 0 && i < I) {
+        float v = 2.f * s[(int64_t)n * I + i] * (part[0][threadIdx.x] + part[1][threadIdx.x] +
+                                                 part[2][threadIdx.x] + part[3][threadIdx.x]);
+        if (add) {
+            asm volatile("" : "+v"(v));
+            v = add[(int64_t)n * I + i] + v;
+        }
+        gs[(int64_t)n * I + i] = v;
+    }
+}
+__global__ __launch_bounds__(256) void demod_bwd_s_kernel(float* gs, const float* dd, const float* d, const float* s,
+                                                          const float* wsq, int N, int O, int I) {
+    __shared__ float lds[1024 + 4 * 64];
+    demod_bwd_s_body(lds, blockIdx.x, blockIdx.y, gs, dd, d, s, wsq, N, O, I, nullptr);
 }
 
 // Multi-tensor kernels of the optimiser step.  A launch walks a block table: entry = (segment << 40) | start,
@@ -274,28 +306,31 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
     return is_max ? nanmax(nanmax(red[0], red[1]), nanmax(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void infnorm_fwd_kernel(float* __restrict__ y, float* __restrict__ nrm,
-                                                          const float* __restrict__ t, int L, float c, int mode) {
-    __shared__ float red[4];
-    const float* tr = t + (int64_t)blockIdx.x * L;
+__device__ __forceinline__ void infnorm_fwd_body(float* red, int row, float* __restrict__ y, float* __restrict__ nrm,
+                                                 const float* __restrict__ t, int L, float c, int mode) {
+    const float* tr = t + (int64_t)row * L;
     float m = 0.f;
     for (int i = threadIdx.x; i < L; i += 256) m = nanmax(m, fabsf(tr[i]));
     m = block_reduce(m, red, true);
-    if (threadIdx.x == 0) nrm[blockIdx.x] = m;
-    float* yr = y + (int64_t)blockIdx.x * L;
+    if (threadIdx.x == 0) nrm[row] = m;
+    float* yr = y + (int64_t)row * L;
     const float k = (1.0f / m) * c;
     for (int i = threadIdx.x; i < L; i += 256) yr[i] = mode == 0 ? tr[i] * k : tr[i] / m;
+}
+__global__ __launch_bounds__(256) void infnorm_fwd_kernel(float* __restrict__ y, float* __restrict__ nrm,
+                                                          const float* __restrict__ t, int L, float c, int mode) {
+    __shared__ float red[4];
+    infnorm_fwd_body(red, blockIdx.x, y, nrm, t, L, c, mode);
 }
 
 // First-order gradient: dt = dy * k + [|t| == n] sgn(t) g_n / cnt, g_n = -(k / n) sum_i dy t, with k = c / n
 // (mode 0) or 1 / n (mode 1; the direct term as dy / n); cnt = the number of maxima (torch's
 // infinity-norm backward splits the gradient evenly between ties).
-__global__ __launch_bounds__(256) void infnorm_bwd_kernel(float* __restrict__ dt, const float* __restrict__ dy,
-                                                          const float* __restrict__ t, const float* __restrict__ nrm,
-                                                          int L, float c, int mode) {
-    __shared__ float red[4];
-    const int64_t base = (int64_t)blockIdx.x * L;
-    const float n = nrm[blockIdx.x];
+__device__ __forceinline__ void infnorm_bwd_body(float* red, int row, float* __restrict__ dt,
+                                                 const float* __restrict__ dy, const float* __restrict__ t,
+                                                 const float* __restrict__ nrm, int L, float c, int mode) {
+    const int64_t base = (int64_t)row * L;
+    const float n = nrm[row];
     float s1 = 0.f, cnt = 0.f;
     for (int i = threadIdx.x; i < L; i += 256) {
         const float tv = t[base + i];
@@ -312,6 +347,12 @@ __global__ __launch_bounds__(256) void infnorm_bwd_kernel(float* __restrict__ dt
         if (fabsf(tv) == n || tv != tv) d += (tv > 0.f ? gm : (tv < 0.f ? -gm : (tv != tv ? tv : 0.f)));
         dt[base + i] = d;
     }
+}
+__global__ __launch_bounds__(256) void infnorm_bwd_kernel(float* __restrict__ dt, const float* __restrict__ dy,
+                                                          const float* __restrict__ t, const float* __restrict__ nrm,
+                                                          int L, float c, int mode) {
+    __shared__ float red[4];
+    infnorm_bwd_body(red, blockIdx.x, dt, dy, t, nrm, L, c, mode);
 }
 
 // Second order of the path-length pass (networks_stylegan2._DemodVJP / _InfNormVJP): the backward of the
@@ -401,6 +442,63 @@ __global__ __launch_bounds__(256) void infnorm_vjp_kernel(float* __restrict__ g_
             if (fabsf(tv) == n || tv != tv) e = (tv > 0.f ? 1.f : (tv < 0.f ? -1.f : (tv != tv ? tv : 0.f))) / cnt;
             g_t[base + i] = e * a - dv * b;
         }
+    }
+}
+
+// The style path of a whole synthesis pass in table launches (sg2_style_table): the weight / style
+// pre-normalisations, the demodulation coefficients and their first-order gradients were one to four launches of
+// a few kilobytes per layer and pass, each bound by its launch.  A job is one single-layer launch: workgroup b
+// serves block b - block0[j] of the job j with block0[j] <= b < block0[j + 1] and runs that kernel's body, so every
+// output is bitwise the single-layer kernel's.  The jobs of one call are independent of each other (a caller
+// with dependent stages makes one call per stage); the table travels in the kernel arguments, as PackTable does.
+// 40 jobs a launch: 40 x 96 bytes + the count are 3,848 bytes of kernel arguments, under the 4 KiB a launch may pass.
+// The dynamically indexed table stays in the kernel-argument segment (gfx950 code object of this kernel: private
+// segment 0 bytes, no scratch enabled, 45 VGPRs / 60 SGPRs, no spills): the job fields are wave-uniform loads.
+constexpr int STYLE_PER_LAUNCH = 40;
+struct StyleJobK {
+    void* p[6];
+    int n[4];
+    int st[3];
+    float c;
+    int mode, kind, block0;
+};
+struct StyleTable {
+    StyleJobK j[STYLE_PER_LAUNCH];
+    int count;
+};
+__global__ __launch_bounds__(256) void style_table_kernel(const StyleTable t) {
+    __shared__ float lds[1024 + 4 * 64];
+    const int b = blockIdx.x;
+    int lo = 0, hi = t.count - 1;                  // last j with block0 <= b (wave-uniform: scalar loads)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t.j[mid].block0 <= b) lo = mid; else hi = mid - 1;
+    }
+    const StyleJobK& j = t.j[lo];
+    const int r = b - j.block0;
+    switch (j.kind) {
+    case SG2_STYLE_INFNORM_FWD:
+        infnorm_fwd_body(lds, r, (float*)j.p[0], (float*)j.p[1], (const float*)j.p[2], j.n[1], j.c, j.mode);
+        break;
+    case SG2_STYLE_DEMOD_FWD:
+        demod_fwd_body(lds, r, (float*)j.p[0], (float*)j.p[1], (const float*)j.p[2], (const float*)j.p[3], j.n[0],
+                       j.n[1], j.n[2], j.n[3], j.c);
+        break;
+    case SG2_STYLE_DEMOD_BWD_W:
+        demod_bwd_w_body(lds, r, (float*)j.p[0], (const float*)j.p[1], (const float*)j.p[2], (const float*)j.p[3],
+                         (const float*)j.p[4], j.n[0], j.n[1], j.n[2], j.n[3], (const float*)j.p[5], j.st[0], j.st[1],
+                         j.st[2]);
+        break;
+    case SG2_STYLE_DEMOD_BWD_S: {
+        const int nby = (j.n[2] + 63) / 64;          // blocks of 64 i per sample, as the single launch's grid y
+        demod_bwd_s_body(lds, r / nby, r % nby, (float*)j.p[0], (const float*)j.p[1], (const float*)j.p[2],
+                         (const float*)j.p[3], (const float*)j.p[4], j.n[0], j.n[1], j.n[2], (const float*)j.p[5]);
+        break;
+    }
+    default:   // SG2_STYLE_INFNORM_BWD (the host admits no other kind)
+        infnorm_bwd_body(lds, r, (float*)j.p[0], (const float*)j.p[1], (const float*)j.p[2], (const float*)j.p[3],
+                         j.n[1], j.c, j.mode);
+        break;
     }
 }
 
@@ -575,6 +673,63 @@ extern "C" int sg2_infnorm_bwd(float* dt, const float* dy, const float* t, const
     SG2_CHECK(rows > 0 && L > 0 && (mode == 0 || mode == 1), "sg2_infnorm_bwd: bad arguments");
     infnorm_bwd_kernel<<<rows, 256, 0, as_stream(stream)>>>(dt, dy, t, nrm, L, c, mode);
     return launch_status("sg2_infnorm_bwd");
+}
+
+extern "C" int sg2_style_table(const sg2_style_job* jobs, int n, void* stream) {
+    using namespace sg2;
+    SG2_CHECK(jobs != nullptr && n > 0, "sg2_style_table: empty table");
+    hipStream_t s = as_stream(stream);
+    for (int i0 = 0; i0 < n; i0 += STYLE_PER_LAUNCH) {
+        StyleTable t{};
+        t.count = std::min(STYLE_PER_LAUNCH, n - i0);
+        int64_t blk = 0;
+        for (int k = 0; k < t.count; ++k) {
+            const sg2_style_job& j = jobs[i0 + k];
+            int64_t nb = 0;
+            switch (j.kind) {
+            case SG2_STYLE_INFNORM_FWD:
+                SG2_CHECK(j.p[0] && j.p[1] && j.p[2], "sg2_style_table: infnorm_fwd: null pointer");
+                SG2_CHECK(j.n[0] > 0 && j.n[1] > 0 && (j.mode == 0 || j.mode == 1), "sg2_style_table: infnorm_fwd: bad arguments");
+                nb = j.n[0];
+                break;
+            case SG2_STYLE_DEMOD_FWD:
+                SG2_CHECK(j.p[0] && j.p[2] && j.p[3], "sg2_style_table: demod_fwd: null pointer");
+                SG2_CHECK(j.n[2] <= 1024 && j.n[2] > 0 && j.n[1] > 0 && j.n[0] > 0 && j.n[3] > 0,
+                          "sg2_style_table: demod_fwd: unsupported shape");
+                nb = j.n[1];
+                break;
+            case SG2_STYLE_DEMOD_BWD_W:
+            case SG2_STYLE_DEMOD_BWD_S:
+                SG2_CHECK(j.p[0] && j.p[1] && j.p[2] && j.p[3] && j.p[4], "sg2_style_table: demod_bwd: null pointer");
+                SG2_CHECK(j.n[2] <= 1024 && j.n[1] <= 1024 && j.n[0] <= 1024 && j.n[2] > 0 && j.n[1] > 0 && j.n[0] > 0 &&
+                          (j.kind == SG2_STYLE_DEMOD_BWD_S || j.n[3] > 0), "sg2_style_table: demod_bwd: unsupported shape");
+                SG2_CHECK(j.st[0] >= 0 && j.st[1] >= 0 && j.st[2] >= 0, "sg2_style_table: demod_bwd: negative stride");
+                nb = j.kind == SG2_STYLE_DEMOD_BWD_W ? (int64_t)j.n[1] : (int64_t)j.n[0] * ((j.n[2] + 63) / 64);
+                break;
+            case SG2_STYLE_INFNORM_BWD:
+                SG2_CHECK(j.p[0] && j.p[1] && j.p[2] && j.p[3], "sg2_style_table: infnorm_bwd: null pointer");
+                SG2_CHECK(j.n[0] > 0 && j.n[1] > 0 && (j.mode == 0 || j.mode == 1), "sg2_style_table: infnorm_bwd: bad arguments");
+                nb = j.n[0];
+                break;
+            default:
+                SG2_CHECK(false, "sg2_style_table: unknown job kind");
+            }
+            SG2_CHECK(blk + nb < (1LL << 31), "sg2_style_table: too many workgroups");
+            StyleJobK& d = t.j[k];
+            for (int q = 0; q < 6; ++q) d.p[q] = j.p[q];
+            for (int q = 0; q < 4; ++q) d.n[q] = j.n[q];
+            for (int q = 0; q < 3; ++q) d.st[q] = j.st[q];
+            d.c = j.c;
+            d.mode = j.mode;
+            d.kind = j.kind;
+            d.block0 = (int)blk;
+            blk += nb;
+        }
+        style_table_kernel<<<(unsigned)blk, 256, 0, s>>>(t);
+        const int rc = launch_status("sg2_style_table");
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------ statistic moments

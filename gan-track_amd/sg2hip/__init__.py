@@ -84,6 +84,8 @@ SIGNATURES = {
     'sg2_infnorm_fwd': [_vp, _vp, _vp, _i, _i, _f, _i, _vp],
     'sg2_infnorm_bwd': [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp],
     'sg2_infnorm_vjp_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp],
+    # (additive to ABI 11: the style path's single-layer launches as jobs of table launches, csrc/misc.hip)
+    'sg2_style_table': [_vp, _i, _vp],
     'sg2_pack_weight': [_vp, _i, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _i, _f, _vp],
     'sg2_pack_weight_multi': [_vp, _i, _vp],
     'sg2_knn_scratch_bytes': [_c_i64p, _i64, _i64, _i],

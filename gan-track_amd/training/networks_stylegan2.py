@@ -14,6 +14,8 @@ MI355X-specific execution choices (numerically equivalent to the reference up to
     contraction regrouped (verified equal to 7e-15 in fp64, SURVEY 8(c)) and is computed this way;
   * demodulation uses sum_i s_i^2 * sum_k W_oik^2 -- no [N,O,I,k,k] temporary.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -199,6 +201,165 @@ def _demod(weight, styles):
         return _Demod.apply(weight, styles)
     wsq = weight.float().square().sum(dim=[2, 3])                 # [O, I]
     return (styles.float().square() @ wsq.t() + 1e-8).rsqrt()     # [N, O]
+
+
+# The style path of a whole synthesis pass in table launches (sg2_style_table).  Per layer and pass the route above
+# runs sg2_infnorm_fwd twice (fp16 layers) and sg2_demod_fwd, and in the first-order backward sg2_demod_bwd (two
+# launches), sg2_infnorm_bwd twice and autograd's two adds of w_n's and s_n's gradient pairs: a few kilobytes each,
+# bound by their launches.  Every layer's styles are known once the grouped affine ran, so all layers' jobs go into
+# one launch per dependent stage -- forward: the pre-normalisations, then the demodulations; backward: the demod
+# gradients (the adds folded in), then the pre-normalisations' -- each job running its single-layer kernel's body, so
+# every value is bitwise the per-layer route's.  SG2_STYLE_TABLE=0 keeps the per-layer route (A/B switch).
+style_table = os.environ.get('SG2_STYLE_TABLE', '1') != '0'
+_JOB = np.dtype([('p', '<u8', (6,)), ('n', '<i4', (4,)), ('st', '<i4', (3,)), ('c', '<f4'), ('mode', '<i4'),
+                 ('kind', '<i4')])    # include/sg2hip.h sg2_style_job (88 bytes)
+_INFNORM_FWD, _DEMOD_FWD, _DEMOD_BWD_W, _DEMOD_BWD_S, _INFNORM_BWD = range(5)
+
+
+def _job(kind, ptrs, n, c=0.0, mode=0, st=(0, 0, 0)):
+    return ([t.data_ptr() if t is not None else 0 for t in ptrs] + [0] * (6 - len(ptrs)),
+            list(n) + [0] * (4 - len(n)), list(st), float(c), mode, kind)
+
+
+def _run_jobs(jobs, device):
+    if jobs:
+        table = np.array(jobs, dtype=_JOB)   # host table: the library copies it into the launch arguments
+        _hip.check(_hip.lib().sg2_style_table(table.ctypes.data, len(jobs), _hip.stream_ptr(device)), 'sg2_style_table')
+
+
+def _add(a, b):
+    return b if a is None else a if b is None else a + b
+
+
+class _StyleTable(torch.autograd.Function):
+    """(prenorm flags, w_0, s_0, w_1, s_1, ...) -> per layer (w_n, s_n, d) where its flag is set (an fp16 layer:
+    _prenorm, then _demod of the normalised pair) or (d,) (_demod alone), all layers in two sg2_style_table calls.
+    The first-order backward is two calls as well; under create_graph (the path-length pass) it returns, layer by
+    layer, what _Demod.backward and _InfNorm.backward return there: the differentiable _DemodVJP / _InfNormVJP nodes
+    or the composed form, over this node's own outputs."""
+
+    @staticmethod
+    def forward(ctx, flags, *tensors):
+        # the inputs themselves are saved (the create_graph backward differentiates through them, as _InfNorm's
+        # saved t_in): a converted copy would carry no autograd history, so anything but contiguous f32 is refused
+        for t in tensors:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError(f'style table: weights and styles must be contiguous float32 tensors, got '
+                                   f'{t.dtype} with strides {tuple(t.stride())}')
+        ws, ss = list(tensors[0::2]), list(tensors[1::2])
+        dev = ss[0].device
+        f32 = dict(dtype=torch.float32, device=dev)
+        stage1, stage2, outs, saved = [], [], [], []
+        for pre, w, s in zip(flags, ws, ss):
+            n, (o, i, kh, kw) = s.shape[0], w.shape
+            wq, sq, nw, ns = w, s, None, None
+            if pre:
+                wq, sq = torch.empty_like(w), torch.empty_like(s)
+                nw, ns = torch.empty([o], **f32), torch.empty([n], **f32)
+                stage1.append(_job(_INFNORM_FWD, (wq, nw, w), (o, i * kh * kw),
+                                   float(np.float32(1 / np.sqrt(i * kh * kw))), 0))
+                stage1.append(_job(_INFNORM_FWD, (sq, ns, s), (n, i), 1.0, 1))
+            d, wsq = torch.empty([n, o], **f32), torch.empty([o, i], **f32)
+            stage2.append(_job(_DEMOD_FWD, (d, wsq, sq, wq), (n, o, i, kh * kw), 1e-8))
+            outs += [wq, sq, d] if pre else [d]
+            saved += [w, s, d, wsq] + ([wq, sq, nw, ns] if pre else [])
+        _run_jobs(stage1, dev)
+        _run_jobs(stage2, dev)
+        ctx.save_for_backward(*saved)
+        ctx.flags = flags
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        saved, grads = list(ctx.saved_tensors), list(grads)
+        graph = torch.is_grad_enabled()
+        need = ctx.needs_input_grad[1:]
+        stage1, stage2, out, layers = [], [], [], []
+        for k, pre in enumerate(ctx.flags):
+            w, s, d, wsq = saved[:4]
+            wq, sq, nw, ns = saved[4:8] if pre else (w, s, None, None)
+            saved = saved[8 if pre else 4:]
+            g_wq, g_sq, dd = (grads[:3] if pre else (None, None, grads[0]))
+            grads = grads[3 if pre else 1:]
+            need_w, need_s = need[2 * k], need[2 * k + 1]
+            if graph:
+                out += _style_backward_graph(pre, need_w, need_s, w, s, d, wsq, wq, sq, nw, ns, g_wq, g_sq, dd)
+                continue
+            n, (o, i, kh, kw) = s.shape[0], w.shape
+            kk = kh * kw
+            if dd is not None:
+                dd = dd.float().contiguous()
+                if need_w:
+                    add, st = g_wq, (0, 0, 0)
+                    if add is not None:
+                        if add.dtype != torch.float32 or add.stride(2) != kw * add.stride(3):
+                            add = add.float().contiguous()
+                        st = (add.stride(0), add.stride(1), add.stride(3))
+                    keep = add
+                    g_wq = torch.empty_like(w)
+                    stage1.append(_job(_DEMOD_BWD_W, (g_wq, dd, d, sq, wq, add), (n, o, i, kk), st=st))
+                    layers.append((keep, dd))    # (alive until the launches are issued)
+                if need_s:
+                    add = g_sq.float().contiguous() if g_sq is not None else None
+                    g_sq = torch.empty_like(s)
+                    stage1.append(_job(_DEMOD_BWD_S, (g_sq, dd, d, sq, wsq, add), (n, o, i)))
+                    layers.append((add, dd))
+            g_w = g_wq if need_w else None
+            g_s = g_sq if need_s else None
+            if pre and g_w is not None:
+                g_wq = g_w.float().contiguous()
+                g_w = torch.empty_like(w)
+                stage2.append(_job(_INFNORM_BWD, (g_w, g_wq, w, nw), (o, i * kk),
+                                   float(np.float32(1 / np.sqrt(i * kk))), 0))
+                layers.append((g_wq,))
+            if pre and g_s is not None:
+                g_sq = g_s.float().contiguous()
+                g_s = torch.empty_like(s)
+                stage2.append(_job(_INFNORM_BWD, (g_s, g_sq, s, ns), (n, i), 1.0, 1))
+                layers.append((g_sq,))
+            out += [g_w, g_s]
+        if not graph:
+            dev = ctx.saved_tensors[0].device
+            _run_jobs(stage1, dev)
+            _run_jobs(stage2, dev)
+        return (None, *out)
+
+
+def _style_backward_graph(pre, need_w, need_s, w, s, d, wsq, wq, sq, nw, ns, g_wq, g_sq, dd):
+    """One layer of _StyleTable.backward under create_graph: _Demod.backward's grad-mode branch, autograd's sums of
+    the gradient pairs, then _InfNorm.backward's."""
+    if dd is not None:
+        nw_d = need_w and not conv2d_gradfix.weight_gradients_disabled
+        if need_s and not nw_d:
+            g_sq = _add(g_sq, _DemodVJP.apply(dd, d, wq, sq, wsq))
+        else:
+            gu = dd * d.pow(3) * -0.5
+            if need_s:
+                g_sq = _add(g_sq, 2 * sq * (gu @ wq.square().sum([2, 3])))
+            if nw_d:
+                g_wq = _add(g_wq, 2 * wq * (gu.t() @ sq.square())[:, :, None, None])
+    g_w = g_wq if need_w else None
+    g_s = g_sq if need_s else None
+    if pre and g_w is not None:
+        o, i, kh, kw = w.shape
+        g_w = _InfNormVJP.apply(g_w.reshape(o, -1), w.reshape(o, -1), nw, float(np.float32(1 / np.sqrt(i * kh * kw))),
+                                0).reshape(w.shape)
+    if pre and g_s is not None:
+        g_s = _InfNormVJP.apply(g_s, s, ns, 1.0, 1)
+    return [g_w, g_s]
+
+
+def style_table_pass(layers):
+    """layers: [(weight [O, I, kh, kw], styles [N, I], prenorm)] of one synthesis pass -> per layer (weight, styles,
+    dcoefs) as _prenorm (where prenorm) and _demod give them, from one _StyleTable node."""
+    flags = tuple(bool(p) for _, _, p in layers)
+    outs = list(_StyleTable.apply(flags, *[t for w, s, _ in layers for t in (w, s)]))
+    res = []
+    for (w, s, pre) in layers:
+        res.append(tuple(outs[:3]) if pre else (w, s, outs[0]))
+        outs = outs[3 if pre else 1:]
+    return res
 
 
 def modulated_conv2d(x, weight, styles, noise=None, up=1, down=1, padding=0, resample_filter=None,
@@ -498,8 +659,17 @@ class SynthesisLayer(torch.nn.Module):
             self.noise_strength = torch.nn.Parameter(torch.zeros([]))
         self.bias = torch.nn.Parameter(torch.zeros([out_channels]))
 
-    def forward(self, x, w, noise_mode='random', fused_modconv=True, gain=1, styles=None):
-        """styles: this layer's affine(w), when the network computed it (grouped_styles)."""
+    def table_ok(self, batch):
+        """Whether the layer, on a device tensor, takes the fused route that consumes (weight, styles, dcoefs) of
+        style_table_pass (forward's own test, less what only x tells: x.is_cuda) within the kernels' shape limits."""
+        o, i = self.weight.shape[:2]
+        fused = modconv.enabled and (self.up == 1 or (self.up == 2 and self.resample_filter.ndim == 2 and o % 8 == 0))
+        return fused and self.activation == 'lrelu' and max(o, i, batch) <= 1024
+
+    def forward(self, x, w, noise_mode='random', fused_modconv=True, gain=1, styles=None, pre=None):
+        """styles: this layer's affine(w), when the network computed it (grouped_styles).  pre: the layer's
+        (weight, styles, dcoefs) of style_table_pass -- pre-normalised where x is fp16 -- in place of the layer's own
+        _prenorm / _demod calls."""
         assert noise_mode in ['random', 'const', 'none']
         misc.assert_shape(x, [None, self.in_channels, self.resolution // self.up, self.resolution // self.up])
         if styles is None:
@@ -514,19 +684,27 @@ class SynthesisLayer(torch.nn.Module):
         if self.activation == 'lrelu' and (up_fused or (self.up == 1 and modconv.supported_generic(x, self.weight))):
             # one-kernel modulated conv + demod + noise + bias + lrelu + clamp (sg2_conv3x3 / sg2_conv2d_fused)
             weight = self.weight
-            if x.dtype == torch.float16:   # fp16 range pre-normalisation (:52-54)
-                weight, styles = _prenorm(weight, styles)
+            if pre is not None:
+                weight, styles, dcoefs = pre
+                assert (weight is not self.weight) == (x.dtype == torch.float16)
+            else:
+                if x.dtype == torch.float16:   # fp16 range pre-normalisation (:52-54)
+                    weight, styles = _prenorm(weight, styles)
+                dcoefs = _demod(weight, styles)
             if noise is not None and noise.ndim == 2:
                 noise = noise.reshape(1, 1, *noise.shape).expand(x.shape[0], 1, -1, -1)
             clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
             if up_fused:
-                return modconv.up_modconv_layer(x, styles, weight, _demod(weight, styles), noise, self.bias,
+                return modconv.up_modconv_layer(x, styles, weight, dcoefs, noise, self.bias,
                                                 self.resample_filter,
                                                 alpha=bias_act.activation_funcs[self.activation].def_alpha,
                                                 gain=self.act_gain * gain, clamp=clamp)
-            return modconv.modconv_layer(x, styles, weight, _demod(weight, styles), noise, self.bias,
+            return modconv.modconv_layer(x, styles, weight, dcoefs, noise, self.bias,
                                          alpha=bias_act.activation_funcs[self.activation].def_alpha,
                                          gain=self.act_gain * gain, clamp=clamp)
+        # (table_ok states the routing test above without x: had the two drifted apart, a table entry computed for this
+        # layer would be dropped here unseen and its work done twice)
+        assert pre is None, 'SynthesisLayer.table_ok admitted a layer that does not take the fused route'
         x = modulated_conv2d(x=x, weight=self.weight, styles=styles, noise=noise, up=self.up, padding=self.padding,
                              resample_filter=self.resample_filter, flip_weight=(self.up == 1),
                              fused_modconv=fused_modconv)
@@ -620,9 +798,13 @@ class SynthesisBlock(torch.nn.Module):
             out.append((self.torgb.affine, k, float(self.torgb.weight_gain)))
         return out
 
-    def forward(self, x, img, ws, force_fp32=False, fused_modconv=None, update_emas=False, styles=None,
+    def conv_layers(self):
+        return ([self.conv0] if self.in_channels != 0 else []) + [self.conv1]
+
+    def forward(self, x, img, ws, force_fp32=False, fused_modconv=None, update_emas=False, styles=None, pre=None,
                 **layer_kwargs):
-        """styles: the layers' styles in w order (SynthesisNetwork's grouped_styles), or None (per-layer affine)."""
+        """styles: the layers' styles in w order (SynthesisNetwork's grouped_styles), or None (per-layer affine).
+        pre: per conv layer, its (weight, styles, dcoefs) of style_table_pass or None."""
         misc.assert_shape(ws, [None, self.num_conv + self.num_torgb, self.w_dim])
         if styles is not None:
             s_iter = iter(styles)
@@ -630,6 +812,7 @@ class SynthesisBlock(torch.nn.Module):
         else:
             s_iter = iter([None] * (self.num_conv + self.num_torgb))
             w_iter = iter(ws.unbind(dim=1))
+        p_iter = iter(pre if pre is not None else [None] * self.num_conv)
         dtype = self.fp16_dtype if self.use_fp16 and not force_fp32 else torch.float32
         if fused_modconv is None:
             fused_modconv = self.fused_modconv_default
@@ -642,16 +825,16 @@ class SynthesisBlock(torch.nn.Module):
             misc.assert_shape(x, [None, self.in_channels, self.resolution // 2, self.resolution // 2])
             x = x.to(dtype=dtype, memory_format=_CL)
         if self.in_channels == 0:
-            x = self.conv1(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), **layer_kwargs)
+            x = self.conv1(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), pre=next(p_iter), **layer_kwargs)
         elif self.architecture == 'resnet':
             y = self.skip(x, gain=np.sqrt(0.5))
-            x = self.conv0(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), **layer_kwargs)
+            x = self.conv0(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), pre=next(p_iter), **layer_kwargs)
             x = self.conv1(x, next(w_iter), fused_modconv=fused_modconv, gain=np.sqrt(0.5), styles=next(s_iter),
-                           **layer_kwargs)
+                           pre=next(p_iter), **layer_kwargs)
             x = y.add_(x)
         else:
-            x = self.conv0(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), **layer_kwargs)
-            x = self.conv1(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), **layer_kwargs)
+            x = self.conv0(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), pre=next(p_iter), **layer_kwargs)
+            x = self.conv1(x, next(w_iter), fused_modconv=fused_modconv, styles=next(s_iter), pre=next(p_iter), **layer_kwargs)
         if img is not None:
             misc.assert_shape(img, [None, self.img_channels, self.resolution // 2, self.resolution // 2])
             img = upfirdn2d.upsample2d(img, self.resample_filter)
@@ -705,15 +888,37 @@ class SynthesisNetwork(torch.nn.Module):
                 block = getattr(self, f'b{r}')
                 plan += [(a, w_idx + k, g) for a, k, g in block.style_layers()]
                 w_idx += block.num_conv
-            styles = iter(grouped_styles(ws, plan))
+            styles = grouped_styles(ws, plan)
+        pre = self._style_table(styles, ws.shape[0], block_kwargs.get('force_fp32', False)) \
+            if styles is not None and style_table else None
+        styles = iter(styles) if styles is not None else None
         w_idx = 0
         for r in self.block_resolutions:
             block = getattr(self, f'b{r}')
             cur = ws.narrow(1, w_idx, block.num_conv + block.num_torgb)
             w_idx += block.num_conv
             bs = [next(styles) for _ in block.style_layers()] if styles is not None else None
-            x, img = block(x, img, cur, styles=bs, **block_kwargs)
+            x, img = block(x, img, cur, styles=bs, pre=pre[r] if pre is not None else None, **block_kwargs)
         return img
+
+    def _style_table(self, styles, batch, force_fp32):
+        """{resolution: per conv layer (weight, styles, dcoefs) or None}: every demodulated layer's style-side
+        quantities of this pass from one style_table_pass (styles: grouped_styles' list, in w order)."""
+        jobs, slots, k = [], {}, 0
+        for r in self.block_resolutions:
+            block = getattr(self, f'b{r}')
+            fp16 = block.use_fp16 and not force_fp32 and block.fp16_dtype == torch.float16
+            slots[r] = []
+            for layer in block.conv_layers():
+                if layer.table_ok(batch):
+                    slots[r].append(len(jobs))
+                    jobs.append((layer.weight, styles[k], fp16))
+                else:
+                    slots[r].append(None)
+                k += 1
+            k += block.num_torgb
+        res = style_table_pass(jobs) if jobs else []
+        return {r: [res[j] if j is not None else None for j in v] for r, v in slots.items()}
 
     def extra_repr(self):
         return (f'w_dim={self.w_dim:d}, num_ws={self.num_ws:d}, img_resolution={self.img_resolution:d}, '

@@ -369,6 +369,30 @@ int sg2_infnorm_fwd(float* y, float* nrm, const float* t, int rows, int L, float
 int sg2_infnorm_bwd(float* dt, const float* dy, const float* t, const float* nrm, int rows, int L, float c, int mode,
                     void* stream);
 
+/* The style path of a whole synthesis pass in table launches (csrc/misc.hip).  ADDITIVE entry point:
+ * SG2_ABI_VERSION stays 11.  `jobs` is a HOST array of n sg2_style_job (copied into the launches' kernel arguments,
+ * 40 jobs per launch, so the call can be captured into a hipGraph).  A job is one launch of a single-layer entry
+ * point and gives bitwise its result; the jobs of one call must not depend on each other.
+ *   kind                    is              p[0..5]                       n[0..3]         c     mode   workgroups
+ *   SG2_STYLE_INFNORM_FWD   sg2_infnorm_fwd y, nrm, t                     rows, L         c     mode   rows
+ *   SG2_STYLE_DEMOD_FWD     sg2_demod_fwd   d, wsq (or NULL), s, w        N, O, I, KK     eps   -      O
+ *   SG2_STYLE_DEMOD_BWD_W   sg2_demod_bwd   gw, dd, d, s, w, add          N, O, I, KK     -     -      O
+ *   SG2_STYLE_DEMOD_BWD_S   sg2_demod_bwd   gs, dd, d, s, wsq, add        N, O, I         -     -      N ceil(I/64)
+ *   SG2_STYLE_INFNORM_BWD   sg2_infnorm_bwd dt, dy, t, nrm                rows, L         c     mode   rows
+ * add (NULL: none): a second gradient of the same tensor, added to the job's result as a separate f32 add would (the
+ * sum autograd makes of a tensor's two gradients); for gw its element (o, i, k) is at add[o st[0] + i st[1] + k st[2]],
+ * for gs it is contiguous [N, I]. */
+enum { SG2_STYLE_INFNORM_FWD = 0, SG2_STYLE_DEMOD_FWD = 1, SG2_STYLE_DEMOD_BWD_W = 2, SG2_STYLE_DEMOD_BWD_S = 3,
+       SG2_STYLE_INFNORM_BWD = 4 };
+typedef struct sg2_style_job {
+    void* p[6];
+    int n[4];
+    int st[3];
+    float c;
+    int mode, kind;
+} sg2_style_job;
+int sg2_style_table(const sg2_style_job* jobs, int n, void* stream);
+
 /* Backward of sg2_infnorm_bwd (ABI 7; the path-length pass's second order through the fp16 pre-normalisation,
  * reference: autograd of networks_stylegan2.py:52-54 under create_graph).  With the first-order gradient
  * dt = c dy / n - c P e / n^2, P = sum dy t, e = sgn(t) [|t| = n] / cnt, and g = dL/ddt [rows, L]:

@@ -23,7 +23,8 @@ def cat(n):
                       ('conv3x3_up2', 'up-2 conv 16-bit'), ('conv3x3_c64p', 'halo conv 16-bit C=64 persistent'), ('conv3x3_c64r', 'ring conv 16-bit C=64'), ('conv3x3_halo', 'halo conv 16-bit'), ('wgrad3x3', 'halo wgrad 16-bit'),
                       ('conv_fwd_kernel<float', 'generic conv f32'), ('conv_fwd_kernel', 'generic conv 16-bit'),
                       ('conv_wgrad_kernel<float', 'generic wgrad f32'), ('conv_wgrad_kernel', 'generic wgrad 16-bit'),
-                      ('layer_bwd', 'layer_bwd'), ('bias_act', 'bias_act'), ('demod', 'demod'), ('Cijk', 'GEMM'),
+                      ('layer_bwd', 'layer_bwd'), ('bias_act', 'bias_act'),
+                      ('style_table', 'style table (demod + pre-normalisation jobs)'), ('demod', 'demod'), ('Cijk', 'GEMM'),
                       ('conv_finalize', 'conv finalize'), ('rocclr', 'memset/copy'), ('zero_fill', 'memset/copy'), ('multi_tensor', 'optimizer'),
                       ('adam_multi', 'optimizer'), ('lerp_multi', 'optimizer'),
                       ('pack_weight', 'weight pack'), ('infnorm', 'fp16 pre-normalisation'),
