@@ -170,8 +170,8 @@ __device__ __forceinline__ void halo_direct_epilogue(const Conv3Args& a, const f
 }
 
 // TW: tile width (pixels); TH = 256 / TW.  4 waves, each owns 64 consecutive tile pixels x 64 channels.
-// NBUF = 2: double-buffered chunks (1 workgroup / CU); NBUF = 1: single buffer, 2 workgroups / CU
-// overlap each other's staging (better when Cin spans only a couple of chunks).
+// One LDS buffer, two workgroups per CU that overlap each other's staging (a double-buffered single workgroup per
+// CU measured 1.3-1.4x slower at C >= 128 and was retired).
 // S = 2: the stride-2, padding-0 3x3 conv (conv2d_resample's down-2 plan after its FIR, :94-109; the D
 // blocks' conv1 and the input gradient of the G up layers) on a 32 x 4 output tile: the (2 TW + 1) x
 // (2 TH + 1) input halo is stored column-deinterleaved (a halo row = its even columns, then its odd ones),
@@ -180,15 +180,14 @@ __device__ __forceinline__ void halo_direct_epilogue(const Conv3Args& a, const f
 // staged in p_chan order, so a lane's accumulators hold 8 consecutive output channels of one pixel and the epilogue
 // stores 16 bytes per lane straight from registers -- no output tile through LDS, no epilogue barrier (the dot
 // reduction: 16-lane shuffles, LDS atomics, one global atomic per channel).
-template <typename T, int TW, bool SCALE_IN, bool EPI, int NBUF, int S = 1, bool DIR = false>
-__global__ __launch_bounds__(256, 3 - NBUF) void conv3x3_halo_kernel(Conv3Args a) {   // NBUF = 1: two workgroups per CU
+template <typename T, int TW, bool SCALE_IN, bool EPI, int S = 1, bool DIR = false>
+__global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(Conv3Args a) {
     static_assert(!DIR || S == 1, "the direct epilogue is the stride-1 form");
     constexpr int TH = S == 1 ? 256 / TW : 4;
     constexpr int PXW = TW * TH / 4, NFR = PXW / 16;                 // pixels and 16-pixel fragments per wave
     constexpr int HW_ = S * (TW - 1) + 3, HH = S * (TH - 1) + 3, HP = HW_ * HH;   // halo pixels
     constexpr int HEV = (HW_ + 1) / 2;                                // even columns of a halo row (S = 2)
     constexpr int HALO = HP * PX;                                      // elements per halo buffer
-    constexpr int WTS = 9 * BN * PX;                                   // elements per weight buffer
     constexpr int NH = (HP * 4 + 255) / 256;                          // halo 16-B loads per thread
     constexpr int NW = (9 * BN * 4) / 256;                            // weight 16-B loads per thread (= 9)
     typedef T vec8 __attribute__((ext_vector_type(8)));
@@ -258,8 +257,8 @@ __global__ __launch_bounds__(256, 3 - NBUF) void conv3x3_halo_kernel(Conv3Args a
             sc1 = *(const float4*)(sc + 4);
         }
     };
-    auto sstore = [&](int buf) {
-        T* hb = smem + buf * (HALO + WTS);
+    auto sstore = [&] {
+        T* hb = smem;
         T* wb = hb + HALO;
         const float scl[8] = {sc0.x, sc0.y, sc0.z, sc0.w, sc1.x, sc1.y, sc1.z, sc1.w};
 #pragma unroll
@@ -294,13 +293,12 @@ __global__ __launch_bounds__(256, 3 - NBUF) void conv3x3_halo_kernel(Conv3Args a
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     gload(0);
-    sstore(0);
+    sstore();
     __syncthreads();
     for (int ch = 0; ch < nchunks; ++ch) {
-        const int cur = NBUF == 2 ? (ch & 1) : 0;
         const bool more = ch + 1 < nchunks;
         if (more) gload(ch + 1);
-        const char* hb = (const char*)(smem + cur * (HALO + WTS));
+        const char* hb = (const char*)smem;
         const char* wb = hb + HALO * sizeof(T) + b_lane;
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -320,8 +318,8 @@ __global__ __launch_bounds__(256, 3 - NBUF) void conv3x3_halo_kernel(Conv3Args a
                     for (int j = 0; j < 4; ++j) acc[i][j] = DIR ? mma<T>(bfr[j], af[i], acc[i][j]) : mma<T>(af[i], bfr[j], acc[i][j]);
             }
         }
-        if (NBUF == 1 && more) __syncthreads();   // everyone done reading before the overwrite
-        if (more) sstore(NBUF == 2 ? (cur ^ 1) : 0);
+        if (more) __syncthreads();   // everyone done reading before the overwrite
+        if (more) sstore();
         __syncthreads();
     }
 
@@ -463,12 +461,12 @@ int launch_halo_tiles(K kern, size_t lds, const Conv3Args& a, hipStream_t s) {
     return launch_status("sg2_conv3x3");
 }
 
-template <typename T, int TW, bool SI, bool EPI, int NBUF, int S = 1, bool DIR = false>
+template <typename T, int TW, bool SI, bool EPI, int S = 1, bool DIR = false>
 int launch3_k(const Conv3Args& a, hipStream_t s) {
     constexpr int TH = S == 1 ? 256 / TW : 4;
-    size_t lds = NBUF * (size_t)((S * (TW - 1) + 3) * (S * (TH - 1) + 3) * PX + 9 * BN * PX) * sizeof(T);
+    size_t lds = (size_t)((S * (TW - 1) + 3) * (S * (TH - 1) + 3) * PX + 9 * BN * PX) * sizeof(T);
     if (!DIR) lds = std::max(lds, (size_t)2 * TW * TH * (BN + 8) * sizeof(T) + BN * sizeof(float));   // epilogue tiles
-    auto kern = conv3x3_halo_kernel<T, TW, SI, EPI, NBUF, S, DIR>;
+    auto kern = conv3x3_halo_kernel<T, TW, SI, EPI, S, DIR>;
     static bool attr_set = false;   // benign race: idempotent attribute
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -477,16 +475,16 @@ int launch3_k(const Conv3Args& a, hipStream_t s) {
     return launch_halo_tiles(kern, lds, a, s);
 }
 
-template <typename T, int TW, bool SI, bool EPI, int NBUF, int S = 1>
+template <typename T, int TW, bool SI, bool EPI, int S = 1>
 int launch3(const Conv3Args& a, hipStream_t s) {
     if constexpr (S == 1) {
         // the direct epilogue (SG2_HALO_DIRECT=0: the LDS-transposed one); read per launch: tests switch it
         const char* e = getenv("SG2_HALO_DIRECT");
         if ((!e || atoi(e) != 0) && a.Cout % BN == 0 && ((uintptr_t)a.y % 16) == 0 && ((uintptr_t)a.y_raw % 16) == 0 &&
             ((uintptr_t)a.dot_src % 16) == 0)
-            return launch3_k<T, TW, SI, EPI, NBUF, 1, true>(a, s);
+            return launch3_k<T, TW, SI, EPI, 1, true>(a, s);
     }
-    return launch3_k<T, TW, SI, EPI, NBUF, S, false>(a, s);
+    return launch3_k<T, TW, SI, EPI, S, false>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -879,10 +877,10 @@ int num_cus() {
 // computing waves (load -> wait -> modulate -> ds_write), so each CU had ~39 KB of HBM reads in flight and the
 // memory phases added to the MFMA phase instead of hiding under it.  Here:
 //   * the weights live in REGISTERS: wave w owns output channels 32 (w & 1) .. +31 (two A fragments per tap and
-//     chunk: 36 x 16 B = 144 VGPRs), so the whole LDS is a 3-slot ring of 32 x 8 pixel tiles (10 x 40 halo
-//     positions of whole 128-byte pixel lines, 51,200 B a slot) -- two tiles (~100 KB) in flight per CU;
+//     chunk: 36 x 16 B = 144 VGPRs), so the whole LDS is a 2-slot ring of 32 x 4 pixel tiles (6 x 40 halo
+//     positions of whole 128-byte pixel lines, 30,720 B a slot) -- one tile being read, one in flight;
 //   * the halo arrives by LDS-DMA (buffer_load ... lds, 16 B a lane, one 1 KiB wave-instruction = 8 whole pixel
-//     lines), issued two tiles ahead, with no register and no LDS-store pass; out-of-image pixels are buffer
+//     lines), issued one tile ahead, with no register and no LDS-store pass; out-of-image pixels are buffer
 //     out-of-range loads, which land as zeros.  The DMA destination is lane-linear, so the bank swizzle sits in
 //     the SOURCE address: the 16-byte piece j of position p is stored at j ^ (((p >> 1) & 3) << 1) (conflict-free
 //     ds_read_b128 of 16 consecutive positions at any tap shift; the 40-position row pitch keeps p mod 8 a
@@ -892,32 +890,35 @@ int num_cus() {
 //     rounded once either way);
 //   * the tile's noise and demodulation scales arrive by a 1 KiB LDS-DMA into a 4-deep epilogue ring;
 //   * one barrier per tile and counted vmcnt waits (never 0 in the loop);
-//   * (default form, TH = 4) two workgroups of 4 waves per CU, each on its own 32 x 4 tiles with a 2-slot ring,
-//     so that a SIMD's two waves belong to workgroups that drift apart: one's MFMAs run beside the other's
-//     epilogue VALU, stores and barrier wait (measured: the memory streams alone -- the halo DMA 0.053 ms, the
-//     stores at 7 TB/s, tools/membench.py -- are well under the kernel time; its one-workgroup 8-wave form
-//     spent the difference with both waves of a SIMD in the same phase).
+//   * two workgroups of 4 waves per CU, each on its own 32 x 4 tiles, so that a SIMD's two waves belong to
+//     workgroups that drift apart: one's MFMAs run beside the other's epilogue VALU, stores and barrier wait
+//     (measured: the memory streams alone -- the halo DMA 0.053 ms, the stores at 7 TB/s, tools/membench.py --
+//     are well under the kernel time).
 // Wave w: rows 2 (w >> 1), +1 of the tile (4 pixel fragments of 16) x its 32 channels: per tap and chunk 4
 // ds_read_b128 (pixels) feed 8 MFMAs (weights from registers).
-constexpr int R_TW = 32, R_PITCH = 40;
-constexpr int R_EPI = 1024, R_NEPI = 4;               // noise [TH x 32] T at 0, demod [64] f32 at 512
-// Two forms (template TH): TH = 8 -- 32 x 8 tiles, 8 waves, one workgroup per CU, a 3-slot ring (two tiles in
-// flight); TH = 4 -- 32 x 4 tiles, 4 waves, TWO workgroups per CU, each with a 2-slot ring.  The waves of a
-// workgroup meet at one barrier per tile, so in the one-workgroup form a SIMD's two waves reach their MFMA,
-// epilogue and barrier phases together; two workgroups drift apart and one's MFMAs run beside the other's
-// epilogue, stores and barrier wait.
-template <int TH, int WR> struct Ring {
-    static constexpr int NW = 2 * TH / WR;                            // waves: 2 channel halves x TH / WR row groups
-    static constexpr int NSLOT = TH == 8 ? 3 : 2;
-    static constexpr int HPOS = (TH + 2) * R_PITCH;                   // halo positions (34 used per row)
-    static constexpr int SLOT = HPOS * 128;                           // 51,200 / 30,720 B
-    static constexpr int HALO_I = HPOS / 8;                           // halo DMA wave-instructions per tile
-    static constexpr int DMA = (HALO_I + 1 + NW - 1) / NW;            // per wave and tile (+ the epilogue table)
-    static constexpr size_t LDS = (size_t)NSLOT * SLOT + R_NEPI * R_EPI + 64 * 4 + 16;   // + gain * bias [64], a broadcast word
-    static constexpr int WGS_PER_CU = TH == 8 ? 1 : 2;
-    static_assert(LDS * WGS_PER_CU <= 160 * 1024, "ring LDS");
-    static_assert((DMA - 1) * NW <= HALO_I && DMA * NW > HALO_I, "the last DMA round holds the epilogue table");
-};
+// One form, launched with the per-sample dynamic tail (DYN, below) where its plan exists and with a static split
+// of the tiles otherwise.  What else was tried on the bench roofline launch, and retired:
+//   * 32 x 8 tiles, one workgroup of 8 waves per CU and a 3-slot ring: a SIMD's two waves reached their MFMA,
+//     epilogue and barrier phases together, 0.162 ms against 0.157 (profiles/r03_ring_forms.txt);
+//   * 32 x 8 tiles, one workgroup of 4 waves with 4 rows each (one wave per SIMD): 0.172 ms (same file);
+//   * whole-line stores staged through the consumed slot (two to four more barriers a tile): 0.164 ms (same file);
+//   * the DMA addresses computed per instruction (a runtime division, a row-validity branch and per-lane kill
+//     logic, ~20 instructions each) instead of hoisted: 0.160-0.165 ms against 0.153-0.157 hoisted and 0.1425
+//     with the dynamic tail (profiles/r05_ring_forms.txt);
+//   * tile k - 1's epilogue beside tile k's MFMAs in one basic block: spilled at 512 registers with the weights in
+//     VGPRs and never ran.
+constexpr int R_TW = 32, R_TH = 4, R_PITCH = 40;
+constexpr int R_WR = 2;                                 // tile rows per wave
+constexpr int R_NW = 2 * R_TH / R_WR;                   // 4 waves: 2 channel halves x 2 row groups
+constexpr int R_NSLOT = 2;
+constexpr int R_EPI = 1024, R_NEPI = 4;                 // noise [TH x 32] T at 0, demod [64] f32 at 512
+constexpr int R_HPOS = (R_TH + 2) * R_PITCH;            // halo positions (34 used per row)
+constexpr int R_SLOT = R_HPOS * 128;                    // 30,720 B
+constexpr int R_HALO_I = R_HPOS / 8;                    // halo DMA wave-instructions per tile
+constexpr int R_DMA = (R_HALO_I + 1 + R_NW - 1) / R_NW; // per wave and tile (+ the epilogue table)
+constexpr size_t R_LDS = (size_t)R_NSLOT * R_SLOT + R_NEPI * R_EPI + 64 * 4 + 16;   // + gain * bias [64], a broadcast word
+static_assert(R_LDS * 2 <= 160 * 1024, "ring LDS: two workgroups per CU");
+static_assert((R_DMA - 1) * R_NW <= R_HALO_I && R_DMA * R_NW > R_HALO_I, "the last DMA round holds the epilogue table");
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 #ifndef SG2_RDIAG
@@ -951,7 +952,7 @@ __device__ __forceinline__ void wait_vm() {           // s_waitcnt vmcnt(N) (gfx
     __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 
-// STG & 16: a dynamic tail within each sample.  The ring kernel is persistent with a static split of the tiles, and
+// DYN: a dynamic tail within each sample.  The ring kernel is persistent with a static split of the tiles, and
 // the CUs do not run at one speed (the in-kernel clock differs by ~8 % between XCDs under this load and the
 // slowest workgroup of a launch ended ~17 % after the median one, tools/ring_stamps.py).  Here the workgroups of a
 // sample (grid / N of them, dealt round-robin over the XCDs) keep static runs of `dyn.s_per_wg` tiles and take the
@@ -974,13 +975,11 @@ struct RingDyn {
 constexpr int RQ_SLOTS = 64, RQ_MAXN = 4096;
 __device__ int g_ring_q[RQ_SLOTS * 2 * RQ_MAXN];
 
-template <typename T, bool SI, bool EPI, bool RAW, int R_TH, int WR, bool PIPE, int STG>
-__global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER_CU)) void conv3x3_c64r_kernel(Conv3Args a, int tiles_total, int band, RingDyn dyn) {
+template <typename T, bool SI, bool EPI, bool RAW, bool DYN>
+__global__ __launch_bounds__(R_NW * 64, 2) void conv3x3_c64r_kernel(Conv3Args a, int tiles_total, int band, RingDyn dyn) {
     typedef T vec8 __attribute__((ext_vector_type(8)));
-    typedef Ring<R_TH, WR> RG;
-    constexpr int NF = 2 * WR;                        // pixel fragments (16 px) per wave
-    constexpr int R_NSLOT = RG::NSLOT, R_SLOT = RG::SLOT, R_HALO_I = RG::HALO_I, R_DMA = RG::DMA, NW = RG::NW;
-    constexpr int S = (RAW ? 2 : 1) * 2 * WR;         // buffer stores per wave and tile
+    constexpr int NF = 2 * R_WR;                      // pixel fragments (16 px) per wave
+    constexpr int S = (RAW ? 2 : 1) * 2 * R_WR;       // buffer stores per wave and tile
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     char* epil = smem_raw + R_NSLOT * R_SLOT;
     float* blds = (float*)(epil + R_NEPI * R_EPI);
@@ -988,8 +987,7 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, q = lane >> 4;
-    const int h = wave & 1, wr = wave >> 1;           // channel half, tile row group (rows WR wr .. + WR - 1)
-    constexpr bool DYN = (STG & 16) != 0;
+    const int h = wave & 1, wr = wave >> 1;           // channel half, tile row group (rows R_WR wr .. + R_WR - 1)
     const int dyn_n = DYN ? (int)blockIdx.x / dyn.wg_per_n : 0;                       // the workgroup's sample
     const int dyn_per_n = DYN ? tiles_total / a.N : 0;
     const int t_begin = DYN ? dyn_n * dyn_per_n + ((int)blockIdx.x - dyn_n * dyn.wg_per_n) * dyn.s_per_wg
@@ -1075,97 +1073,59 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
     load_weights(cur_n);
     if (tid < 64) blds[tid] = (EPI && a.bias) ? (float)(T)a.bias[tid] * a.gain : 0.f;
 
-    // ---- LDS-DMA issue: wave w owns instructions i = u * NW + w, u < R_DMA ----
+    // ---- LDS-DMA issue: R_DMA instructions per wave and tile ----
     const bool has_noise = EPI && a.noise != nullptr, has_d = EPI && a.out_scale != nullptr;
     const char* epi_src0 = has_noise ? (const char*)a.noise : (has_d ? (const char*)a.out_scale : (const char*)a.x);
     const char* epi_src1 = has_d ? (const char*)a.out_scale : epi_src0;
-    // Instruction i < 50 loads halo row hy = i / 5, columns (i % 5) * 8 + lane / 8 (8 whole pixel lines); the
+    // Instruction i < 30 loads halo row hy = i / 5, columns (i % 5) * 8 + lane / 8 (8 whole pixel lines); the
     // stored piece lane % 8 holds global piece j = (lane % 8) ^ swizzle, a function of the lane only (the column
     // group adds a multiple of 8).  Row validity is wave-uniform; column validity per lane.
     const int lx = lane >> 3;
     const int hlane = lx * 128 + (((lane & 7) ^ (((lx >> 1) & 3) << 1)) * 16);
-    // epilogue table: lanes 0-31 the tile's noise (row (lane / 4) mod TH, 16-byte piece lane % 4; with TH = 4 lanes
-    // 16-31 repeat rows 0-3 into the unused rows 4-7 of the table), lanes 32-63 the sample's demodulation scales
+    // epilogue table: lanes 0-31 the tile's noise (row (lane / 4) mod TH, 16-byte piece lane % 4; lanes 16-31
+    // repeat rows 0-3 into the unused rows 4-7 of the table), lanes 32-63 the sample's demodulation scales
     // (16 bytes a lane; lanes 48-63 repeat 32-47 into the unused tail of the table)
     // (without noise the first half reads the start of whichever buffer stands in for it: always in bounds)
     const int elane = lane < 32 ? (has_noise ? (((lane >> 2) % R_TH) * a.W + (lane & 3) * 8) * (int)sizeof(T) : 0)
                                 : ((lane - 32) & 15) * 16;
-    auto issue = [&](int t, int slot, int eslot) {
-        if (SG2_RDIAG & 16) return;                   // timing-only build: no loads
-        int n, ty, tx;
-        tile_of(t, n, ty, tx);
-#pragma unroll
-        for (int u = 0; u < R_DMA; ++u) {
-            const int i = u * NW + wave;              // wave-uniform; u < R_DMA - 1: always a halo instruction
-            if (u < R_DMA - 1 || i < R_HALO_I) {
-                const int hy = i / 5, cg = i - hy * 5;
-                const int iy = ty - 1 + hy, ix0 = tx - 1 + cg * 8;
-                // uniform row base; a row outside the image gets a negative base (every lane out of range: zeros).
-                // Per lane the image's left / right border column reads zeros, and the pad lanes (column 34 .. 39
-                // of the halo row, never read) read nothing: an out-of-range lane moves no bytes (15 % of the
-                // halo's requests)
-                const int base = (unsigned)iy < (unsigned)a.H ? ((n * a.H + iy) * a.W + ix0) * 128 : -(1 << 30);
-                const bool kill = ((tx == 0) & (cg == 0) & (lx == 0)) | ((tx + R_TW == a.W) & (cg == 4) & (lx == 1)) |
-                                  (!(SG2_RDIAG & 128) & (cg == 4) & (lx >= 2));
-                const int off = kill ? -1 : base + hlane;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rxb, (lds_ptr_t)(smem_raw + slot * R_SLOT + i * 1024), 16, off, 0, 0, 0);
-            } else {                                  // the epilogue table (duplicates write the same bytes)
-                const char* nb = has_noise ? epi_src0 + (int64_t)((n * a.H + ty) * a.W + tx) * (int)sizeof(T) : epi_src0;
-                const char* db = has_d ? epi_src1 + n * 256 : epi_src1;
-                const char* src = (lane < 32 ? nb : db) + elane;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (lds_ptr_t)(epil + eslot * R_EPI), 16, 0, 0);
-            }
-        }
-    };
-
-    // STG & 4 (TH = 4, 4 waves): the same DMAs with the tile-independent parts of their addresses hoisted out of the
-    // loop and every column group a compile-time constant of the instruction: wave w loads halo row w (column groups
-    // 0..4), then waves 0 / 1 row 4 / 5 column groups 0..2 and waves 2 / 3 row 4 / 5 column groups 3, 4 and the
-    // epilogue table (both: duplicates write the same bytes).  Per DMA: one scalar add for the row base (twice a
-    // tile), one vector add, a select on the border columns only -- where the generic issue above spends ~20
-    // instructions (a runtime division, the row-validity branch and the per-lane kill logic) on each.
+    // The tile-independent parts of the DMA addresses are hoisted out of the loop and every column group is a
+    // compile-time constant of the instruction: wave w loads halo row w (column groups 0..4), then waves 0 / 1 row
+    // 4 / 5 column groups 0..2 and waves 2 / 3 row 4 / 5 column groups 3, 4 and the epilogue table (both: duplicates
+    // write the same bytes).  Per DMA: one scalar add for the row base (twice a tile), one vector add, a select on
+    // the border columns only.  Row validity is wave-uniform: a row outside the image gets base INT_MIN (every lane
+    // out of range: zeros).  Per lane the image's left / right border column reads zeros, and the pad lanes (column
+    // 34 .. 39 of the halo row, never read) read nothing: an out-of-range lane moves no bytes (15 % of the halo's
+    // requests).
     const int rs_w = a.W * 128;
     auto issue_fast_at = [&](int n, int ty, int tx, int slot, int eslot) {
-        if constexpr (R_TH == 4 && NW == 4) {
-            if (SG2_RDIAG & 16) return;
-            const int base0 = ((n * a.H + ty - 1) * a.W + tx - 1) * 128;     // halo row 0, column -1
-            const int rowA = wave, rowB = 4 + (wave & 1);
-            // an invalid row: every lane out of range (INT_MIN + < 8 KiB stays above any buffer of < 2^31 - 2^16 B)
-            const int bA = (rowA == 0 && ty == 0) ? (int)0x80000000 : base0 + rowA * rs_w;
-            const int bB = (rowB == R_TH + 1 && ty + R_TH == a.H) ? (int)0x80000000 : base0 + rowB * rs_w;
-            const bool killL = (tx == 0) & (lx == 0);
-            const bool killR = (!(SG2_RDIAG & 128) & (lx >= 2)) | ((tx + R_TW == a.W) & (lx == 1));
-            char* sb = smem_raw + slot * R_SLOT;
-            auto dma = [&](int b, int row, int cg) {
-                int off = b + cg * 1024 + hlane;
-                if (cg == 0) off = killL ? -1 : off;
-                if (cg == 4) off = killR ? -1 : off;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rxb, (lds_ptr_t)(sb + (row * 5 + cg) * 1024), 16, off, 0, 0, 0);
-            };
+        if (SG2_RDIAG & 16) return;                   // timing-only build: no loads
+        const int base0 = ((n * a.H + ty - 1) * a.W + tx - 1) * 128;     // halo row 0, column -1
+        const int rowA = wave, rowB = 4 + (wave & 1);
+        // an invalid row: every lane out of range (INT_MIN + < 8 KiB stays above any buffer of < 2^31 - 2^16 B)
+        const int bA = (rowA == 0 && ty == 0) ? (int)0x80000000 : base0 + rowA * rs_w;
+        const int bB = (rowB == R_TH + 1 && ty + R_TH == a.H) ? (int)0x80000000 : base0 + rowB * rs_w;
+        const bool killL = (tx == 0) & (lx == 0);
+        const bool killR = (!(SG2_RDIAG & 128) & (lx >= 2)) | ((tx + R_TW == a.W) & (lx == 1));
+        char* sb = smem_raw + slot * R_SLOT;
+        auto dma = [&](int b, int row, int cg) {
+            int off = b + cg * 1024 + hlane;
+            if (cg == 0) off = killL ? -1 : off;
+            if (cg == 4) off = killR ? -1 : off;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rxb, (lds_ptr_t)(sb + (row * 5 + cg) * 1024), 16, off, 0, 0, 0);
+        };
 #pragma unroll
-            for (int cg = 0; cg < 5; ++cg) dma(bA, rowA, cg);
-            if (wave < 2) {
+        for (int cg = 0; cg < 5; ++cg) dma(bA, rowA, cg);
+        if (wave < 2) {
 #pragma unroll
-                for (int cg = 0; cg < 3; ++cg) dma(bB, rowB, cg);
-            } else {
-                dma(bB, rowB, 3);
-                dma(bB, rowB, 4);
-                const char* nb = has_noise ? epi_src0 + (int64_t)((n * a.H + ty) * a.W + tx) * (int)sizeof(T) : epi_src0;
-                const char* db = has_d ? epi_src1 + n * 256 : epi_src1;
-                const char* src = (lane < 32 ? nb : db) + elane;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (lds_ptr_t)(epil + eslot * R_EPI), 16, 0, 0);
-            }
-        }
-    };
-    auto issue_any = [&](int t, int slot, int eslot) {
-        if constexpr ((STG & 4) != 0) {
-            int n, ty, tx;
-            tile_of(t, n, ty, tx);
-            issue_fast_at(n, ty, tx, slot, eslot);
+            for (int cg = 0; cg < 3; ++cg) dma(bB, rowB, cg);
         } else {
-            issue(t, slot, eslot);
+            dma(bB, rowB, 3);
+            dma(bB, rowB, 4);
+            const char* nb = has_noise ? epi_src0 + (int64_t)((n * a.H + ty) * a.W + tx) * (int)sizeof(T) : epi_src0;
+            const char* db = has_d ? epi_src1 + n * 256 : epi_src1;
+            const char* src = (lane < 32 ? nb : db) + elane;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                             (lds_ptr_t)(epil + eslot * R_EPI), 16, 0, 0);
         }
     };
 
@@ -1177,7 +1137,7 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
             const int x = l16 + kx;
-            boff[kx][c] = (WR * wr * R_PITCH + x) * 128 + 16 * ((c * 4 + q) ^ (((x >> 1) & 3) << 1));
+            boff[kx][c] = (R_WR * wr * R_PITCH + x) * 128 + 16 * ((c * 4 + q) ^ (((x >> 1) & 3) << 1));
         }
 
     const float lr_alpha = (EPI && a.act == 1) ? a.alpha : 1.f;
@@ -1204,8 +1164,8 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
             bb[e] = bq[e];
             dd[e] = has_d ? dq[e] * a.gain : a.gain;
         }
-        // pixel (WR wr + (i >> 1)) * 32 + (i & 1) * 16 + l16 of the table: byte offset 32 i from na
-        const unsigned na = et + (WR * wr * R_TW + l16) * (unsigned)sizeof(T);
+        // pixel (R_WR wr + (i >> 1)) * 32 + (i & 1) * 16 + l16 of the table: byte offset 32 i from na
+        const unsigned na = et + (R_WR * wr * R_TW + l16) * (unsigned)sizeof(T);
 #pragma unroll
         for (int g = 0; g < NF / 4; ++g) {
             unsigned r0, r1, r2, r3;
@@ -1218,13 +1178,12 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
                 nz[4 * g + j] = has_noise ? (float)__builtin_bit_cast(T, (unsigned short)rr[j]) * ngain : 0.f;
         }
     };
-    // the epilogue math and stores of one tile from its accumulators: pure VALU + buffer stores, no branch, so
-    // in the pipelined form it shares a basic block (and the scheduler's interleave) with the next tile's MFMAs
+    // the epilogue math and stores of one tile from its accumulators: pure VALU + buffer stores, no branch
     auto epi_store = [&](f32x4 (&A)[NF][2], int n, int ty, int tx, const float (&bb)[8], const float (&dd)[8],
                          const float (&nz)[NF]) {
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
-            const int r = WR * wr + (i >> 1), px = (i & 1) * 16 + l16;
+            const int r = R_WR * wr + (i >> 1), px = (i & 1) * 16 + l16;
             const int pix = (n * a.H + ty + r) * a.W + tx + px;
             vec8 yv, rv;
 #pragma unroll
@@ -1241,67 +1200,9 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
             }
             int dst = (pix * 64 + ch0) * (int)sizeof(T) | -(int)((SG2_RDIAG & 32) != 0);   // timing-only build: dropped
             if (SG2_RDIAG & 256)   // timing-only build: the same bytes as whole-line stores (8 px x 128 B an instruction)
-                dst = (((n * a.H + ty + WR * wr + h) * a.W + tx + i * 8 + (lane >> 3)) * 64 + (lane & 7) * 8) * (int)sizeof(T);
+                dst = (((n * a.H + ty + R_WR * wr + h) * a.W + tx + i * 8 + (lane >> 3)) * 64 + (lane & 7) * 8) * (int)sizeof(T);
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, yv), ryb, dst, 0, 0);
             if (RAW) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rv), ryr, dst, 0, 0);
-        }
-    };
-    // STG: the same epilogue with whole-line stores.  The tile's outputs go through the slot its MFMAs just
-    // consumed (free until the next iteration's DMA into it, which follows the loop's last barrier): each wave
-    // writes its 16-byte pieces (8 channels of a pixel) into a [128 px][128 B] image, piece c of pixel P at
-    // c ^ (P & 7) (conflict-free ds_write_b128 and ds_read_b128), then reads back whole 128-byte pixel lines, 8
-    // pixels per wave-instruction, and stores those.  Measured with a timing build (RDIAG 256): the half-line
-    // stores' texture-address cost beside the halo DMAs was 11 % of the launch.  Two more barriers (four with
-    // the raw output, staged in a second round).
-    auto epi_store_staged = [&](f32x4 (&A)[NF][2], int slot, int n, int ty, int tx, const float (&bb)[8],
-                                const float (&dd)[8], const float (&nz)[NF]) {
-        if constexpr (WR == 2) {                      // (staged stores: two rows per wave pair)
-        const unsigned sb = lds_addr(smem_raw + slot * R_SLOT);
-        u32x4 yq[NF], rq[NF];
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            vec8 yv, rv;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float cv = A[i][e >> 2][e & 3];
-                if (RAW) rv[e] = (T)cv;
-                float v = cv;
-                if (EPI) {
-                    v = fmaf(v, dd[e], nz[i] + bb[e]);
-                    v = fmaxf(v, v * lr_alpha);
-                    v = __builtin_amdgcn_fmed3f(v, -clampv, clampv);
-                }
-                yv[e] = (T)v;
-            }
-            yq[i] = __builtin_bit_cast(u32x4, yv);
-            rq[i] = __builtin_bit_cast(u32x4, rv);
-        }
-        auto stage_store = [&](const u32x4 (&v)[NF], const __amdgpu_buffer_rsrc_t& rout) {
-#pragma unroll
-            for (int i = 0; i < NF; ++i) {
-                const int P = (2 * wr + (i >> 1)) * R_TW + (i & 1) * 16 + l16;
-                const unsigned off = sb + P * 128 + (((4 * h + q) ^ (P & 7)) << 4);
-                asm volatile("ds_write_b128 %0, %1" :: "v"(off), "v"(v[i]) : "memory");
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
-            const int c = lane & 7, row = 2 * wr + h;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int px = 8 * j + (lane >> 3), P = row * R_TW + px;
-                u32x4 w;
-                asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(w) : "v"(sb + P * 128 + ((c ^ (P & 7)) << 4)));
-                const int pix = (n * a.H + ty + row) * a.W + tx + px;
-                __builtin_amdgcn_raw_buffer_store_b128(w, rout, (pix * 64 + c * 8) * (int)sizeof(T), 0, 0);
-            }
-        };
-        __builtin_amdgcn_s_waitcnt(0xc07f);           // every wave is done reading the slot's halo
-        __builtin_amdgcn_s_barrier();
-        stage_store(yq, ryb);
-        if (RAW) {
-            __builtin_amdgcn_s_barrier();             // the y image has been read back
-            stage_store(rq, ryr);
-        }
         }
     };
     auto mfma_tile = [&](f32x4 (&A)[NF][2], const char* hb) {
@@ -1326,14 +1227,13 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
                 }
     };
 
-    // ---- prologue: tiles 0 .. NSLOT - 2 in flight, wait for tile 0 ----
-    issue_any(t_begin, 0, 0);
-    if (R_NSLOT == 3) {
-        issue_any(min(t_begin + 1, t_end - 1), 1, 1);
-        wait_vm<R_DMA>();
-    } else {
-        wait_vm<0>();
+    // ---- prologue: tile 0 in flight, wait for it ----
+    {
+        int n, ty, tx;
+        tile_of(t_begin, n, ty, tx);
+        issue_fast_at(n, ty, tx, 0, 0);
     }
+    wait_vm<0>();
     __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0): the bias table
     __builtin_amdgcn_s_barrier();
 
@@ -1347,7 +1247,6 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
 #define RING_STAMP(ph) ((void)0)
 #endif
     if constexpr (DYN) {
-        static_assert(R_NSLOT == 2 && !PIPE, "dynamic tail: the 2-slot form");
         int* qlds = (int*)(blds + 64);               // the broadcast word (16 bytes past the bias table)
         int* qn = dyn.q + dyn_n;                      // this sample's grab counter
         f32x4 acc[NF][2];
@@ -1369,8 +1268,7 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
             const int slot = k % R_NSLOT;
             const int n = cn, ty = cty, tx = ctx;
             if (nxt >= 0) tile_of(nxt, cn, cty, ctx);
-            if constexpr ((STG & 4) != 0) issue_fast_at(cn, cty, ctx, (k + 1) % R_NSLOT, (k + 1) % R_NEPI);
-            else issue(nxt >= 0 ? nxt : cur, (k + 1) % R_NSLOT, (k + 1) % R_NEPI);
+            issue_fast_at(cn, cty, ctx, (k + 1) % R_NSLOT, (k + 1) % R_NEPI);
             RING_STAMP(0);
             mfma_tile(acc, smem_raw + slot * R_SLOT);
             RING_STAMP(1);
@@ -1391,12 +1289,13 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
             if (nxt != cur + 1) rend = nxt + 2;        // a new chunk
             cur = nxt;
         }
-    } else if constexpr (!PIPE) {
+    } else {
         f32x4 acc[NF][2];
         for (int t = t_begin; t < t_end; ++t, ++k) {
             const int slot = k % R_NSLOT;
-            issue_any(min(t + R_NSLOT - 1, t_end - 1), (k + R_NSLOT - 1) % R_NSLOT, (k + R_NSLOT - 1) % R_NEPI);
             int n, ty, tx;
+            tile_of(min(t + 1, t_end - 1), n, ty, tx);
+            issue_fast_at(n, ty, tx, (k + 1) % R_NSLOT, (k + 1) % R_NEPI);
             tile_of(t, n, ty, tx);
             if (SI && n != cur_n) {                   // a new sample: re-modulate the weights (rare)
                 cur_n = n;
@@ -1407,66 +1306,16 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
             RING_STAMP(1);
             float bb[8], dd[8], nz[NF];
             epi_table(k % R_NEPI, bb, dd, nz);
-            if constexpr (STG == 1) epi_store_staged(acc, slot, n, ty, tx, bb, dd, nz);
-            else epi_store(acc, n, ty, tx, bb, dd, nz);
+            epi_store(acc, n, ty, tx, bb, dd, nz);
             RING_STAMP(2);
-            // tile t + 1's DMAs must have landed: everything but the youngest ops of this wave.  3 slots: t + 1
-            // was issued one iteration ago, younger are this iteration's DMAs and stores and the previous
-            // iteration's stores; 2 slots: t + 1 was issued at the top of this iteration, younger are this
-            // iteration's stores
-            if (R_NSLOT == 2) wait_vm<S>();
-            else if (k == 0) wait_vm<R_DMA + S>();
-            else wait_vm<R_DMA + 2 * S>();
+            // tile t + 1's DMAs must have landed: everything but the youngest ops of this wave.  t + 1 was issued
+            // at the top of this iteration, younger are this iteration's stores
+            wait_vm<S>();
             RING_STAMP(3);
             __builtin_amdgcn_s_waitcnt(0xc07f);       // lgkmcnt(0): this tile's LDS reads are done
             __builtin_amdgcn_s_barrier();
             RING_STAMP(4);
         }
-    } else {
-        // Pipelined epilogue (3-slot form): iteration k runs tile k's MFMAs into one accumulator set and tile
-        // k - 1's epilogue from the other in the same basic block, so the epilogue's VALU and stores issue
-        // between MFMAs instead of after them.  The epilogue table of tile k - 1 (its epilogue-ring slot is
-        // rewritten three iterations later) is read at the top of the iteration.
-        static_assert(!PIPE || R_NSLOT == 3, "pipelined epilogue: 3-slot ring");
-        f32x4 acc0[NF][2], acc1[NF][2];
-        int t = t_begin, pn = 0, pty = 0, ptx = 0;
-        auto step = [&](auto has_prev, f32x4 (&Acur)[NF][2], f32x4 (&Aprev)[NF][2]) {
-            constexpr bool HP = decltype(has_prev)::value;
-            const int slot = k % R_NSLOT;
-            issue(min(t + R_NSLOT - 1, t_end - 1), (k + R_NSLOT - 1) % R_NSLOT, (k + R_NSLOT - 1) % R_NEPI);
-            int n, ty, tx;
-            tile_of(t, n, ty, tx);
-            if (SI && n != cur_n) {
-                cur_n = n;
-                load_weights(n);
-            }
-            float bb[8], dd[8], nz[NF];
-            if (HP) epi_table((k + R_NEPI - 1) % R_NEPI, bb, dd, nz);
-            mfma_tile(Acur, smem_raw + slot * R_SLOT);
-            if (HP) epi_store(Aprev, pn, pty, ptx, bb, dd, nz);
-            // tile t + 1's DMAs (issued one iteration ago) must have landed; younger: the stores of the previous
-            // iteration (none at k = 1), this iteration's DMAs and its stores (none at k = 0)
-            if (k == 0) wait_vm<R_DMA>();
-            else if (k == 1) wait_vm<R_DMA + S>();
-            else wait_vm<R_DMA + 2 * S>();
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_s_barrier();
-            pn = n; pty = ty; ptx = tx;
-            ++k; ++t;
-        };
-        step(std::false_type{}, acc0, acc1);
-        bool last0 = true;                            // which set holds the last tile's sums
-        while (t < t_end) {
-            step(std::true_type{}, acc1, acc0);
-            last0 = false;
-            if (t >= t_end) break;
-            step(std::true_type{}, acc0, acc1);
-            last0 = true;
-        }
-        float bb[8], dd[8], nz[NF];
-        epi_table((k + R_NEPI - 1) % R_NEPI, bb, dd, nz);
-        if (last0) epi_store(acc0, pn, pty, ptx, bb, dd, nz);
-        else epi_store(acc1, pn, pty, ptx, bb, dd, nz);
     }
     wait_vm<0>();                                     // no LDS-DMA may outlive the workgroup
     if constexpr (DYN) {
@@ -1483,7 +1332,7 @@ __global__ __launch_bounds__((Ring<R_TH, WR>::NW) * 64, (Ring<R_TH, WR>::WGS_PER
     }
 #if SG2_RDIAG & 512
     {
-        const int gw = blockIdx.x * NW + wave;
+        const int gw = blockIdx.x * R_NW + wave;
         if (lane == 0 && gw < RST_WAVES) {
             unsigned long long* o = g_ring_stamps + gw * RST_F;
             for (int ph = 0; ph < 5; ++ph) o[ph] = st_sum[ph];
@@ -1517,8 +1366,9 @@ int* ring_queue_slot() {
     return b + 2 * RQ_MAXN * (next.fetch_add(1, std::memory_order_relaxed) % RQ_SLOTS);
 }
 
-// The dynamic tail's plan (form 49): static tiles per workgroup, chunk count and the reciprocals of the tile
-// decode.  false when the shape cannot take it (the caller then launches the static form 46).
+// The dynamic tail's plan: static tiles per workgroup, chunk count and the reciprocals of the tile decode.  false
+// when the shape cannot take it (whole samples per workgroup group, >= 8 tiles per workgroup, an even dynamic
+// remainder ...): the launcher then runs the static split.
 // SG2_RING_DYN: percent of a sample's tiles handed out dynamically (default 12), a whole number of 2-tile chunks.
 bool ring_dyn_plan(const Conv3Args& a, int tiles, int grid, int band, RingDyn& dyn) {
     static const int pct = [] { const char* e = getenv("SG2_RING_DYN"); return e ? std::max(0, std::min(50, atoi(e))) : 12; }();
@@ -1538,60 +1388,28 @@ bool ring_dyn_plan(const Conv3Args& a, int tiles, int grid, int band, RingDyn& d
     return true;
 }
 
-template <typename T, bool SI, bool EPI, bool RAW, int TH, int WR, bool PIPE, int STG>
-int launch_c64r(const Conv3Args& a, hipStream_t s, int tiles, int grid, int band) {
-    typedef Ring<TH, WR> RG;
-    auto kern = conv3x3_c64r_kernel<T, SI, EPI, RAW, TH, WR, PIPE, STG>;
-    static bool attr_set = false;   // benign race: idempotent attribute
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RG::LDS);
-        attr_set = true;
-    }
-    RingDyn dyn{nullptr, 0, 0, 0, 0u, 0u, 0};
-    if ((STG & 16) != 0) {     // the caller (launch_c64r_form) checked ring_dyn_plan
-        if (!ring_dyn_plan(a, tiles, grid, band, dyn) || !(dyn.q = ring_queue_slot())) {
-            set_error("sg2_conv3x3 (c64 ring): dynamic tail unavailable");
-            return -1;
-        }
-    }
-    kern<<<grid, RG::NW * 64, RG::LDS, s>>>(a, tiles, band, dyn);
-    return launch_status("sg2_conv3x3 (c64 ring)");
-}
-
-template <typename T, bool SI, bool EPI, int TH, int WR, bool PIPE = false, int STG = 0>
-int launch_c64r_raw(const Conv3Args& a, hipStream_t s, int tiles, int grid, int band) {
-    return a.y_raw ? launch_c64r<T, SI, EPI, true, TH, WR, PIPE, STG>(a, s, tiles, grid, band)
-                   : launch_c64r<T, SI, EPI, false, TH, WR, PIPE, STG>(a, s, tiles, grid, band);
-}
-
-// form: 4 = 32 x 4 tiles, two workgroups of 4 waves per CU; 46 = form 4 with the hoisted DMA issue (issue_fast,
-// the default); 8 = 32 x 8 tiles, one workgroup of 8 waves;
-// 44 = form 4 with whole-line stores staged through the consumed slot; 84 = 32 x 8 tiles, one workgroup of 4
-// waves with 4 rows each (one wave per SIMD, 512 registers).  (The PIPE
-// template form -- tile k - 1's epilogue beside tile k's MFMAs -- spills at 512 registers with the weights in
-// VGPRs and is not instantiated.)
+// The one launcher: the raw output from a.y_raw, the dynamic tail where its plan exists unless the static split was
+// asked for (SG2_C64_RING=46: the fallback's own tests and A/Bs).
 template <typename T, bool SI, bool EPI>
-int launch_c64r_form(const Conv3Args& a, hipStream_t s, int form) {
-    const int th = (form == 4 || form == 44 || form == 46 || form == 49) ? 4 : 8;
-    const int tiles = a.N * (a.H / th) * (a.W / R_TW);
-    const int ty = a.H / th;
+int launch_c64r(const Conv3Args& a, hipStream_t s, bool static_only) {
+    const int ty = a.H / R_TH, tiles = a.N * ty * (a.W / R_TW), grid = 2 * num_cus();
     const int band = ty % 4 == 0 ? 4 : (ty % 2 == 0 ? 2 : 1);
-    if (form == 4) return launch_c64r_raw<T, SI, EPI, 4, 2>(a, s, tiles, 2 * num_cus(), band);
-    if (form == 44) return launch_c64r_raw<T, SI, EPI, 4, 2, false, 1>(a, s, tiles, 2 * num_cus(), band);
-
-    if (form == 46) return launch_c64r_raw<T, SI, EPI, 4, 2, false, 4>(a, s, tiles, 2 * num_cus(), band);
-    if (form == 49) {     // the dynamic tail where its plan exists (whole samples per workgroup group, >= 8 tiles
-                          // per workgroup, an even dynamic remainder ...), else the static form 46
-        const int grid = 2 * num_cus();
-        RingDyn probe{nullptr, 0, 0, 0, 0u, 0u, 0};
-        if (ring_dyn_plan(a, tiles, grid, band, probe))
-            return launch_c64r_raw<T, SI, EPI, 4, 2, false, 20>(a, s, tiles, grid, band);
-        return launch_c64r_raw<T, SI, EPI, 4, 2, false, 4>(a, s, tiles, grid, band);
+    RingDyn dyn{nullptr, 0, 0, 0, 0u, 0u, 0};
+    const bool use_dyn = !static_only && ring_dyn_plan(a, tiles, grid, band, dyn);
+    if (use_dyn && !(dyn.q = ring_queue_slot())) {
+        set_error("sg2_conv3x3 (c64 ring): dynamic tail unavailable");
+        return -1;
     }
-
-
-    if (form == 84) return launch_c64r_raw<T, SI, EPI, 8, 4>(a, s, tiles, num_cus(), band);
-    return launch_c64r_raw<T, SI, EPI, 8, 2>(a, s, tiles, num_cus(), band);
+    auto kern = a.y_raw ? (use_dyn ? conv3x3_c64r_kernel<T, SI, EPI, true, true> : conv3x3_c64r_kernel<T, SI, EPI, true, false>)
+                        : (use_dyn ? conv3x3_c64r_kernel<T, SI, EPI, false, true> : conv3x3_c64r_kernel<T, SI, EPI, false, false>);
+    static bool attr_set[2][2] = {};   // per kernel; benign race: idempotent attribute
+    bool& set = attr_set[a.y_raw != nullptr][use_dyn];
+    if (!set) {
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R_LDS);
+        set = true;
+    }
+    kern<<<grid, R_NW * 64, R_LDS, s>>>(a, tiles, band, dyn);
+    return launch_status("sg2_conv3x3 (c64 ring)");
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2231,9 +2049,9 @@ int dispatch(Conv3Args& a, hipStream_t s, int stride) {
         // 32 x 4 output tiles, two workgroups per CU
         a.tiles_x = (a.OW + 31) / 32;
         a.tiles_y = (a.OH + 3) / 4;
-        if (si) { if (epi) return launch3<T, 32, true, true, 1, 2>(a, s); return launch3<T, 32, true, false, 1, 2>(a, s); }
-        if (epi) return launch3<T, 32, false, true, 1, 2>(a, s);
-        return launch3<T, 32, false, false, 1, 2>(a, s);
+        if (si) { if (epi) return launch3<T, 32, true, true, 2>(a, s); return launch3<T, 32, true, false, 2>(a, s); }
+        if (epi) return launch3<T, 32, false, true, 2>(a, s);
+        return launch3<T, 32, false, false, 2>(a, s);
     }
     static const bool persist = [] { const char* e = getenv("SG2_HALO_PERSIST"); return !e || atoi(e) != 0; }();
     {
@@ -2253,25 +2071,24 @@ int dispatch(Conv3Args& a, hipStream_t s, int stride) {
             return launch_c32r_raw<T, false, false>(a, s);
         }
     }
-    // SG2_C64_RING: 0 off, else the ring form (launch_c64r_form: 49 default -- form 4 with the hoisted DMA issue
-    // and the per-sample dynamic tail, 0.146-0.150 ms on the bench launch against 0.154-0.156 for 46 (hoisted issue
-    // only) and 0.161 for 4, profiles/r05_ring_forms.txt --, 46, 4, 44, 8, 84)
+    // SG2_C64_RING: 0 off; 46 the static split only; unset, 49 or anything else (the values of retired forms
+    // included) the default -- the per-sample dynamic tail where its plan exists, 0.1425 ms on the bench launch
+    // against 0.153-0.157 for the static split, profiles/r05_ring_forms.txt
     const char* ring_env = getenv("SG2_C64_RING");   // read per launch: tests switch forms in one process
     const int ring = ring_env ? atoi(ring_env) : 49;
-    const int rth = (ring == 4 || ring == 44 || ring == 46 || ring == 49) ? 4 : 8;
-    if (ring && !a.dot_out && a.Cin == P_C && a.Cout == P_C && a.H % rth == 0 && a.W % R_TW == 0 &&
+    if (ring && !a.dot_out && a.Cin == P_C && a.Cout == P_C && a.H % R_TH == 0 && a.W % R_TW == 0 &&
         ((uintptr_t)a.y % 16) == 0 && ((uintptr_t)a.y_raw % 16) == 0 && ((uintptr_t)a.noise % 16) == 0 &&
         ((uintptr_t)a.out_scale % 16) == 0 && ((uintptr_t)a.in_scale % 16) == 0 &&
         (!epi || (a.gain > 0.f && (a.act == 0 || (a.alpha >= 0.f && a.alpha <= 1.f))))) {
-        const int tiles = a.N * (a.H / rth) * (a.W / R_TW);
-        const int grid = (rth == 4 ? 2 : 1) * num_cus();
+        const int tiles = a.N * (a.H / R_TH) * (a.W / R_TW);
+        const int grid = 2 * num_cus();
         // (the fast DMA issue marks an invalid halo row with base INT_MIN: the image must stay below 2^31 - 2^16 B)
-        if (tiles >= 2 * grid && tiles <= 128 * grid && a.N < 4096 && a.H / rth < 1024 && a.W / R_TW < 1024 &&
+        if (tiles >= 2 * grid && tiles <= 128 * grid && a.N < 4096 && a.H / R_TH < 1024 && a.W / R_TW < 1024 &&
             (int64_t)a.N * a.H * a.W * 64 * (int64_t)sizeof(T) < 0x7fff0000ll) {
-            const int form = (ring == 84 || ring == 44 || ring == 46 || ring == 49) ? ring : rth;
-            if (si) { if (epi) return launch_c64r_form<T, true, true>(a, s, form); return launch_c64r_form<T, true, false>(a, s, form); }
-            if (epi) return launch_c64r_form<T, false, true>(a, s, form);
-            return launch_c64r_form<T, false, false>(a, s, form);
+            const bool st = ring == 46;
+            if (si) { if (epi) return launch_c64r<T, true, true>(a, s, st); return launch_c64r<T, true, false>(a, s, st); }
+            if (epi) return launch_c64r<T, false, true>(a, s, st);
+            return launch_c64r<T, false, false>(a, s, st);
         }
     }
     // (the persistent kernel's epilogue folds the gain into the demod / noise / bias terms and evaluates lrelu
@@ -2289,18 +2106,16 @@ int dispatch(Conv3Args& a, hipStream_t s, int stride) {
     const int TW = a.W >= 32 ? 32 : 16;
     a.tiles_x = (a.W + TW - 1) / TW;
     a.tiles_y = (a.H + (256 / TW) - 1) / (256 / TW);
-    static const int force_nbuf = [] { const char* e = getenv("SG2_HALO_NBUF"); return e ? atoi(e) : 0; }();
     // one LDS buffer per workgroup: two workgroups per CU (2 waves / SIMD) hide each other's staging and
-    // load latency; measured 1.3-1.4x faster than a double-buffered single workgroup per CU at C >= 128
-    // (gpurun_out/nbuf.log; SG2_HALO_NBUF=2 selects the double-buffered form)
-    const int nbuf = force_nbuf ? force_nbuf : 1;
+    // load latency; measured 1.3-1.4x faster than a double-buffered single workgroup per CU at C >= 128,
+    // which is why the halo kernel has no double-buffered form
     {
         // the LDS-DMA form of the 32 x 8 tile with the direct epilogue (SG2_HALO_DMA=0: off; it stands in for the
-        // direct-epilogue kernel only, so SG2_HALO_DIRECT=0 and SG2_HALO_NBUF keep their meaning); read per launch:
+        // direct-epilogue kernel only, so SG2_HALO_DIRECT=0 keeps its meaning); read per launch:
         // tests and A/Bs switch it in one process
         const char* ed = getenv("SG2_HALO_DMA");
         const char* e1 = getenv("SG2_HALO_DIRECT");
-        if ((!ed || atoi(ed) != 0) && (!e1 || atoi(e1) != 0) && !force_nbuf && TW == 32 && a.Cin % CK == 0 &&
+        if ((!ed || atoi(ed) != 0) && (!e1 || atoi(e1) != 0) && TW == 32 && a.Cin % CK == 0 &&
             a.Cout % BN == 0 && a.Cin <= 16384 && (!si || a.Cin <= D_SCIN) &&
             ((uintptr_t)a.y % 16) == 0 && ((uintptr_t)a.y_raw % 16) == 0 && ((uintptr_t)a.dot_src % 16) == 0 &&
             (int64_t)a.N * a.H * a.W * a.Cin * (int64_t)sizeof(T) < 0x7fff0000ll &&
@@ -2310,15 +2125,14 @@ int dispatch(Conv3Args& a, hipStream_t s, int stride) {
             return launch_halo_dma<T, false, false>(a, s);
         }
     }
-#define L3(TWV, SIV, EPIV) return nbuf == 1 ? launch3<T, TWV, SIV, EPIV, 1>(a, s) : launch3<T, TWV, SIV, EPIV, 2>(a, s)
     if (TW == 32) {
-        if (si) { if (epi) L3(32, true, true); else L3(32, true, false); }
-        else { if (epi) L3(32, false, true); else L3(32, false, false); }
-    } else {
-        if (si) { if (epi) L3(16, true, true); else L3(16, true, false); }
-        else { if (epi) L3(16, false, true); else L3(16, false, false); }
+        if (si) { if (epi) return launch3<T, 32, true, true>(a, s); return launch3<T, 32, true, false>(a, s); }
+        if (epi) return launch3<T, 32, false, true>(a, s);
+        return launch3<T, 32, false, false>(a, s);
     }
-#undef L3
+    if (si) { if (epi) return launch3<T, 16, true, true>(a, s); return launch3<T, 16, true, false>(a, s); }
+    if (epi) return launch3<T, 16, false, true>(a, s);
+    return launch3<T, 16, false, false>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2334,7 +2148,7 @@ int dispatch(Conv3Args& a, hipStream_t s, int stride) {
 //   per tap: 2 pixel and 4 weight fragments, 8 MFMAs into phase (ky & 1, kx & 1).
 // LDS rows are the swizzled 64-byte rows of swz64.  The epilogue transposes each phase through LDS and
 // stores whole 128-byte pixel lines (64 channels).  Two workgroups per CU, single-buffered LDS (the same
-// staging discipline as conv3x3_halo_kernel NBUF = 1).
+// staging discipline as conv3x3_halo_kernel).
 constexpr int U_TW = 16, U_TH = 8, U_CELLS = U_TW * U_TH;              // 128 cells
 constexpr int U_HW = U_TW + 1, U_HH = U_TH + 1, U_HP = U_HW * U_HH;   // 17 x 9 = 153 input positions
 constexpr int U_HB = ((U_HP * 64 + 255) / 256) * 256;                  // halo bytes (256-aligned: swz64)

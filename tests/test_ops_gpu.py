@@ -1797,12 +1797,10 @@ def test_fused_conv_wgain_weight_grad(mode):
 @pytest.mark.parametrize('ring', ['4', '44', '46', '49', '8', '84'])
 def test_conv3x3_c64_ring(dtype, shape, form, ring, monkeypatch):
     """The 64 -> 64 channel ring kernel (LDS-DMA halo ring, weights in registers modulated per sample;
-    conv3x3.hip conv3x3_c64r_kernel) in its three forms (ring 4: two workgroups per CU on 32 x 4 tiles, 2-slot rings;
-    ring 44: ring 4 with whole-line stores staged through LDS; 46 (the default): ring 4 with the hoisted DMA issue;
-    49: ring 46 with a per-sample dynamic tail (engaged at the (8, 256, 256) shape);
-    ring 8: one workgroup of 8 waves on 32 x 8 tiles,
-    3-slot ring; ring 84: the same tiles with 4 waves of 4 rows)
-    and every form the layers use -- the synthesis forward
+    conv3x3.hip conv3x3_c64r_kernel: two workgroups per CU on 32 x 4 tiles, 2-slot rings) with the static split of
+    the tiles (ring 46) and as launched by default (ring 49: a per-sample dynamic tail where its plan exists, engaged
+    at the (8, 256, 256) shape; rings 4, 44, 8 and 84, the values of retired forms, select the default too and are
+    no error) and every form the layers use -- the synthesis forward
     (modulation, demod, noise, bias, lrelu, clamp, raw output), the path-length pass's scaled transposed conv
     (modulation only), the D conv (bias + lrelu + clamp), a plain conv -- against float64.  Shapes cover bands of
     4 / 2 / 1 tile rows, runs that cross samples (the per-sample weight re-modulation) and image borders on every
@@ -1811,8 +1809,8 @@ def test_conv3x3_c64_ring(dtype, shape, form, ring, monkeypatch):
     monkeypatch.setenv('SG2_C64_RING', ring)
     N, H, W = shape
     C = 64
-    th = 4 if ring in ('4', '44', '46', '49') else 8
-    wgs = (2 if th == 4 else 1) * torch.cuda.get_device_properties(DEV).multi_processor_count
+    th = 4
+    wgs = 2 * torch.cuda.get_device_properties(DEV).multi_processor_count
     assert N * (H // th) * (W // 32) >= 2 * wgs      # the ring kernel's minimum of two tiles per workgroup
     t = _c3_inputs('c64_ring', 17, (N, C, H, W, C))
     x, w, s, d, noise, b = (t[k] for k in ('x', 'w', 's', 'd', 'noise', 'b'))
@@ -1863,6 +1861,12 @@ def test_conv3x3_c64_ring_no_dynamic_tail(form, monkeypatch):
     2 x 256 workgroups, but each sample's 27 x 11 = 297 tiles leave an odd remainder after any even number of static
     tiles per workgroup, so the launch takes the static form 46 instead of failing."""
     test_conv3x3_c64_ring(torch.float16, (16, 108, 352), form, '49', monkeypatch)
+
+
+def test_conv3x3_c64_ring_retired_value(monkeypatch):
+    """SG2_C64_RING set to the value of a retired form ('8', once the 32 x 8 tile form) is no error: it computes the
+    default form's result.  (4, 256, 256) is the smallest shape the ring's gate accepts on 256 CUs."""
+    test_conv3x3_c64_ring(torch.float16, (4, 256, 256), 'mod_epi_raw', '8', monkeypatch)
 
 
 @pytest.mark.parametrize('dtype', [torch.float16, torch.bfloat16])

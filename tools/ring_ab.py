@@ -1,5 +1,5 @@
 """Times the 256^2 C=64 fused synthesis-layer launch (bench.py's roofline launch) in this process's kernel
-configuration (SG2_C64_RING, SG2_RING_DBG); prints ms per launch and the fraction of 8 TB/s.  Also the DOT (dgrad)
+configuration (SG2_C64_RING); prints ms per launch and the fraction of 8 TB/s.  Also the DOT (dgrad)
 and plain forms.  Usage: python tools/ring_ab.py [reps]"""
 import os
 import sys
@@ -22,7 +22,7 @@ res = []
 for r in range(int(sys.argv[1]) if len(sys.argv) > 1 else 3):
     ms, fl, by = bench._layer_launch(dev, 256, 64, torch.float16)
     res.append(ms)
-print(f"ring={os.environ.get('SG2_C64_RING', '49')} dbg={os.environ.get('SG2_RING_DBG', '0')} fused launch ms "
+print(f"ring={os.environ.get('SG2_C64_RING', '49')} fused launch ms "
       f"{' '.join(f'{m:.4f}' for m in res)}  best frac {by / (min(res) * 1e-3) / 8e12:.3f}", flush=True)
 # plain conv (D layer form: bias + lrelu, no modulation) and the dgrad DOT form
 N, C, R = 32, 64, 256
